@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: DOF-updates/s of the Linear RK4 step (p=4 hex, fp64) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full classical RK4 step (4 stages: stiffness action + shared-DOF reduction +
 boundary terms + fused stage update) of the Linear acoustic model.
@@ -16,15 +16,19 @@ Workloads (config.workload names the one that ran):
                      (strong scaling; 8 slabs of 32 x 256 x 256), heterogeneous c / rho map.
   --global-cells 256 --P 6 --dtype f32               configs[4].
 All state is resident in HBM when the timed region starts.  The timed region is K steps, bracketed
-by barrier + synchronize; it is repeated --repeats times (each repeat continues the same simulation)
-and `value` comes from the MEDIAN repeat, with min / max beside it.
+by barrier + synchronize; it is repeated --repeats times (each repeat continues the same simulation;
+default 1, with --full 5) and `value` comes from the MEDIAN repeat, with min / max beside it.
+
+A plain run sets up, warms up, times the steps, writes the outputs (--dump-outputs) and prints the
+line.  Everything else below (live HBM traffic, per-kernel HIP events and the roofline built on them,
+the other geometry paths, the CPU baseline, the finite-solution check) runs only with --full.
 
 The headline goes through the library's kernel for general first-order hexahedral meshes (J and G
 recomputed per point from each cell's trilinear map, --geometry trilinear: the synthetic box is not
 allowed its affine shortcut); the reference's data path (per-point G streamed from HBM) and the
 affine path are timed beside it at N=1 ('streamed_geometry', 'other_geometry').
 
-Prints ONE JSON line on rank 0 including
+Prints ONE JSON line on rank 0 including, with --full,
   roofline     -- the dominant kernel (block stiffness operator + fused stage update):
                   `achieved` = algorithmic bytes per launch (rho_e (s + 4 + g) + s per DOF,
                   g = the path's geometry bytes per element-DOF: 6 s streamed, 21 s / N^3 trilinear,
@@ -259,6 +263,7 @@ def live_traffic(argv_tail, P, dtype):
 #  input and reads it (u0 at stage 0, un later): one value more per stage.
 LEAN_INTERIOR = (4, 5, 6, 7)
 EVENT_SAMPLE = 5   # HIP events around every 5th launch of the dominant kernel in the timed region (see run())
+DUMP_SAMPLE = 1 << 21   # values per vector written by --dump-outputs: 16 MiB per fp64 vector
 FULL_INTERIOR = (7, 10, 10, 6)
 LEAN_SHARED = (5, 6, 7, 8)
 
@@ -284,6 +289,18 @@ def compulsory_bytes(info, nc, N3, s, geom, model="linear", lean=True):
     shared = (npairs + (sum(LEAN_SHARED if lean else FULL_INTERIOR) / 4.0 + extra_v) * nsh) * s
     return blk, shared, det
 
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in the run's scalar type.  A vector longer than DUMP_SAMPLE
+    is cut to a fixed seeded sample of DUMP_SAMPLE entries (the same entries for every vector of that length), so
+    that two builds can be compared value for value at any size."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port():
@@ -333,7 +350,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="RK4 steps per timed repeat (default: about 0.26 s per repeat at configs[1])")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed K-step block is run this many times; value = median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed K-step block is run this many times; value = median (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: live HBM traffic (--traffic), per-kernel "
+                         "HIP events and the roofline, the other geometry paths (--both-geometries), the CPU baseline, "
+                         "the finite-solution check; without it these options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last step left (u, v of rank 0's DOFs; a fixed "
+                         "seeded sample of %d entries each when longer) as DIR/<name>.npy" % DUMP_SAMPLE)
     ap.add_argument("--cells", type=int, default=64, help="cells per axis per GPU (weak scaling)")
     ap.add_argument("--cells-xyz", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"),
                     help="cells per GPU as a box NX x NY x NZ instead of --cells^3 (32 256 256 = one rank's x-slab of the "
@@ -390,6 +415,10 @@ def main():
                     help="RK4 steps of the CPU sample; 0 = sized for about 15 s of threaded CPU work")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        args.traffic, args.both_geometries, args.no_cpu, args.no_profile = "none", 0, True, True
 
     # stdout carries exactly one line, the JSON result: whatever libraries print on file descriptor 1
     # (RCCL's start-up banner under torch.distributed.run, for one) is sent to stderr instead
@@ -580,6 +609,9 @@ def main():
             context.set_option("profile_sample", EVENT_SAMPLE)
             context.profile_enable(2)
         times = [timed(steps) for _ in range(repeats)]
+        if headline and args.dump_outputs and rank == 0:
+            model.u_sol()                      # copies u and v of the last step to the host
+            dump_outputs(args.dump_outputs, {"u": model.u_n.x.array, "v": model.v_n.x.array})
         prof = {}
         if profile:
             prof = {k: context.profile_get(k) for k in ("stiffness", "stiffness_if")}
@@ -592,8 +624,10 @@ def main():
             prof["breakdown_ms_per_step"] = {k: context.profile_get(k)[0] / nb for k in
                                              ("stiffness", "stiffness_if", "shared", "boundary", "stage", "halo")}
             context.profile_enable(0)
-        u = model.u_sol().x.array
-        finite = bool(np.isfinite(u).all()) and float(np.abs(u).max()) > 0.0
+        finite = None
+        if args.full:
+            u = model.u_sol().x.array
+            finite = bool(np.isfinite(u).all()) and float(np.abs(u).max()) > 0.0
         model.close()
         if info["diag_metric"]:
             affine = "affine_diag"
@@ -665,7 +699,6 @@ def main():
         lean = (args.lean_rk4 is None or args.lean_rk4 == 1)
         comp_blk, comp_sh, comp_det = compulsory_bytes(info, nc, N3, s, affine, args.model, lean)
         comp_step = 4.0 * (comp_blk + comp_sh) / ndl            # bytes per DOF-update (4 stages)
-        copy_bw = ctx.measure_bandwidth()     # measured streaming bandwidth of this device
         cellsdesc = "x".join(str(k) for k in args.cells_xyz) if args.cells_xyz else f"{args.cells}^3"
         mode = (f"strong scaling: {args.global_cells}^3 box in {world} x-slab(s)" if args.global_cells else
                 f"weak scaling: {cellsdesc} cells per GPU")
@@ -722,42 +755,46 @@ def main():
             "repeats": {"n": len(times), "ms_per_step": ms_rep, "min": min(ms_rep), "max": max(ms_rep),
                         "median": 1e3 * elapsed / args.steps,
                         "value_min": ndofs_counted * args.steps / max(times), "value_max": ndofs_counted * args.steps / min(times)},
-            "roofline": {"bound": "hbm", "kernel": f"k_block_op<{'double' if args.dtype == 'f64' else 'float'},{P},stiffness,+fused RK4 stage>", "achieved": achieved,
-                         "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": tbytes,
-                         # the rate at which the kernel really moves bytes (PMC traffic / HIP-event duration)
-                         "real_traffic_GBps": (tbytes / (avg_ms * 1e-3) / 1e9) if (tbytes and avg_ms > 0) else None,
-                         "frac_real": (tbytes / (avg_ms * 1e-3) / 8e12) if (tbytes and avg_ms > 0) else None,
-                         "traffic_source": traffic_src if tbytes else None,
-                         "traffic_detail": traffic if tbytes else None,
-                         # measured streaming bandwidth of this device (16-byte copy/triad kernel of the library)
-                         "measured_stream_GBps": copy_bw,
-                         "real_traffic_frac_of_measured_stream": (tbytes / (avg_ms * 1e-3) / 1e9 / copy_bw) if (tbytes and avg_ms > 0) else None,
-                         "algorithmic_bytes_per_launch": alg_launch, "interior_dofs": n_int, "avg_launch_ms": avg_ms,
-                         "launches": k_cnt,
-                         "event_sampling": f"HIP events on the library's stream around every {EVENT_SAMPLE}th launch of the kernel inside "
-                                           "the timed region (all four RK4 stage kinds sampled equally); launches = sampled launches",
-                         # what THIS layout must move (compulsory_bytes above): the ceiling this design can be held to.
-                         # `frac` / `achieved` stay SURVEY 8d's accounting figure against the reference's data path --
-                         # an equivalent bandwidth, not a rate of bytes moved; read frac_real / frac_compulsory for that
-                         "compulsory_bytes_per_launch": comp_blk,
-                         "compulsory_detail": comp_det,
-                         "frac_compulsory": (comp_blk / (avg_ms * 1e-3) / 8e12) if avg_ms > 0 else None,
-                         "raw_FETCH_SIZE_bytes_per_launch": (traffic["read_bytes_per_launch"] / 2.0) if (traffic and "read_bytes_per_launch" in traffic) else None,
-                         "fetch_size_correction": "x2 (MI355X_MICROARCH.md, HBM: FETCH_SIZE reports half of a wide coalesced read on gfx950)",
-                         "achieved_is": "algorithmic-equivalent GB/s (SURVEY 8d byte model / time), not bytes moved",
-                         "achieved_exceeds_measured_stream": bool(achieved > copy_bw)},
             "step_roofline": {"algorithmic_bytes_per_dof_update": b_general,
                               "achieved_GBps": b_general * value / world / 1e9,
                               "frac_of_8TBps": b_general * value / world / 8e12,
                               "compulsory_bytes_per_dof_update": comp_step,
                               "compulsory_GBps": comp_step * value / world / 1e9,
                               "frac_compulsory": comp_step * value / world / 8e12},
-            # per-operator-action rate, comparable to the reference's logged stiffness actions
-            # (2.0e9 DOF/s on 76 Icelake cores, p=4 fp64); here one action also does the fused stage update
-            "operator_action_dofs_per_s": (ndl / (avg_ms * 1e-3)) if avg_ms > 0 else None,
-            "kernel_ms_per_step": prof["breakdown_ms_per_step"],
-            "finite_nonzero_solution": finite,
         }
+        if args.full:
+            copy_bw = ctx.measure_bandwidth()     # measured streaming bandwidth of this device
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": f"k_block_op<{'double' if args.dtype == 'f64' else 'float'},{P},stiffness,+fused RK4 stage>", "achieved": achieved,
+                             "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": tbytes,
+                             # the rate at which the kernel really moves bytes (PMC traffic / HIP-event duration)
+                             "real_traffic_GBps": (tbytes / (avg_ms * 1e-3) / 1e9) if (tbytes and avg_ms > 0) else None,
+                             "frac_real": (tbytes / (avg_ms * 1e-3) / 8e12) if (tbytes and avg_ms > 0) else None,
+                             "traffic_source": traffic_src if tbytes else None,
+                             "traffic_detail": traffic if tbytes else None,
+                             # measured streaming bandwidth of this device (16-byte copy/triad kernel of the library)
+                             "measured_stream_GBps": copy_bw,
+                             "real_traffic_frac_of_measured_stream": (tbytes / (avg_ms * 1e-3) / 1e9 / copy_bw) if (tbytes and avg_ms > 0) else None,
+                             "algorithmic_bytes_per_launch": alg_launch, "interior_dofs": n_int, "avg_launch_ms": avg_ms,
+                             "launches": k_cnt,
+                             "event_sampling": f"HIP events on the library's stream around every {EVENT_SAMPLE}th launch of the kernel inside "
+                                               "the timed region (all four RK4 stage kinds sampled equally); launches = sampled launches",
+                             # what THIS layout must move (compulsory_bytes above): the ceiling this design can be held to.
+                             # `frac` / `achieved` stay SURVEY 8d's accounting figure against the reference's data path --
+                             # an equivalent bandwidth, not a rate of bytes moved; read frac_real / frac_compulsory for that
+                             "compulsory_bytes_per_launch": comp_blk,
+                             "compulsory_detail": comp_det,
+                             "frac_compulsory": (comp_blk / (avg_ms * 1e-3) / 8e12) if avg_ms > 0 else None,
+                             "raw_FETCH_SIZE_bytes_per_launch": (traffic["read_bytes_per_launch"] / 2.0) if (traffic and "read_bytes_per_launch" in traffic) else None,
+                             "fetch_size_correction": "x2 (HBM on gfx950: FETCH_SIZE reports half of a wide coalesced read)",
+                             "achieved_is": "algorithmic-equivalent GB/s (SURVEY 8d byte model / time), not bytes moved",
+                             "achieved_exceeds_measured_stream": bool(achieved > copy_bw)},
+                # per-operator-action rate, comparable to the reference's logged stiffness actions
+                # (2.0e9 DOF/s on 76 Icelake cores, p=4 fp64); here one action also does the fused stage update
+                "operator_action_dofs_per_s": (ndl / (avg_ms * 1e-3)) if avg_ms > 0 else None,
+                "kernel_ms_per_step": prof["breakdown_ms_per_step"],
+                "finite_nonzero_solution": finite,
+            })
         # the step's second kernel: stage update of the rank-local shared dofs = their block partial sums (8.. planes at
         # the dof's own index) + the stage's model vectors; RK4 stage kinds 4, 5, 6, 3 stream 5, 7, 10, 6 vectors
         st_ms = prof["breakdown_ms_per_step"].get("stage", 0.0)

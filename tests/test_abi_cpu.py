@@ -8,6 +8,7 @@ import pytest
 
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import _abi
+from util import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,9 +24,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_no_cpu_fallback():
-    import torch
-
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("GPU present")
     with pytest.raises(fa.FusError, match="no HIP device"):
         fa.Context(0)

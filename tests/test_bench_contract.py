@@ -1,6 +1,6 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys plus `roofline` and
-`cpu_baseline`), checked on a small instance of the workload, and its behaviour without a GPU (the
-product has no CPU path: it must stop with an error, not print a number)."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys; with --full also `roofline`
+and `cpu_baseline`), checked on a small instance of the workload, its --dump-outputs files, and its
+behaviour without a GPU (the product has no CPU path: it must stop with an error, not print a number)."""
 import json
 import os
 import subprocess
@@ -8,6 +8,7 @@ import sys
 
 import numpy as np
 import pytest
+from util import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,8 +19,7 @@ def run_bench(*args, timeout=600):
 
 
 def test_bench_refuses_to_run_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("device present")
     out = run_bench("--steps", "1", "--warmup", "0", "--cells", "4", "--no-cpu")
     assert out.returncode != 0
@@ -69,8 +69,7 @@ def test_self_launch_relays_rank0_line_and_exit_code(capsys, monkeypatch):
 
 
 def test_bench_gpus_2_without_gpu_fails_cleanly():
-    import torch
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("device present")
     out = run_bench("--gpus", "2", "--steps", "1", "--warmup", "0", "--cells", "4", "--no-cpu")
     assert out.returncode != 0 and out.stdout.strip() == ""
@@ -82,7 +81,7 @@ def test_bench_two_ranks_self_launched_on_one_box():
     """The N > 1 path end to end through `python bench.py --gpus 2` (self-launch): two distinct rank processes, each
     with its own x-slab, exchanging their interface plane every stage.  On a one-GPU box the two ranks share the
     device and the exchange is staged over gloo (rehearsal); on a multi-GPU box it is the library's RCCL path."""
-    out = run_bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--cells", "8", "--no-cpu",
+    out = run_bench("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--cells", "8", "--no-cpu",
                     "--traffic", "none", timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -99,8 +98,8 @@ def test_bench_two_ranks_self_launched_on_one_box():
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    out = run_bench("--steps", "3", "--warmup", "1", "--repeats", "3", "--cells", "16", "--cpu-n", "8", "--cpu-steps", "5",
-                    "--traffic", "profile")
+    out = run_bench("--full", "--steps", "3", "--warmup", "1", "--repeats", "3", "--cells", "16", "--cpu-n", "8",
+                    "--cpu-steps", "5", "--traffic", "profile")
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1                      # exactly one line on stdout, everything else on stderr
@@ -128,6 +127,50 @@ def test_bench_json_contract():
     # the other geometry paths are timed beside the headline at N = 1
     assert d["other_geometry"]["value"] > 0 and d["streamed_geometry"]["value"] > 0
     assert "trilinear" in d["config"]["geometry"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps once, prints the headline keys only, and --dump-outputs writes the state
+    the last step left; the same arguments give the same inputs, so two runs agree."""
+    runs = []
+    for k in range(2):
+        d_out = tmp_path / f"out{k}"
+        out = run_bench("--steps", "4", "--warmup", "1", "--cells", "8", "--dump-outputs", str(d_out))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        runs.append((json.loads(lines[0]), d_out))
+    d, d_out = runs[0]
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str),
+                     ("ms_per_step", float)):
+        assert isinstance(d[key], typ), key
+    assert d["steps"] == 4 and d["repeats"]["n"] == 1 and d["unit"] == "DOF-updates/s" and d["dtype"] == "f64"
+    ndofs = (8 * 4 + 1) ** 3
+    assert abs(d["value"] - ndofs * 4 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "kernel_ms_per_step", "other_geometry", "streamed_geometry"):
+        assert key not in d, key
+    u0, v0 = np.load(d_out / "u.npy"), np.load(d_out / "v.npy")
+    assert u0.dtype == np.float64 and u0.shape == v0.shape == (ndofs,)
+    assert np.isfinite(u0).all() and np.isfinite(v0).all() and np.abs(u0).max() > 0
+    u1, v1 = np.load(runs[1][1] / "u.npy"), np.load(runs[1][1] / "v.npy")
+    assert np.abs(u1 - u0).max() <= 1e-12 * np.abs(u0).max() and np.abs(v1 - v0).max() <= 1e-12 * np.abs(v0).max()
+
+
+def test_dump_outputs_sample(tmp_path):
+    """--dump-outputs keeps short vectors whole and cuts long ones to the same seeded sample every time."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    short = np.arange(10, dtype=np.float32)
+    long = np.arange(bench.DUMP_SAMPLE + 1000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"s": short, "l": long})
+    bench.dump_outputs(str(tmp_path / "b"), {"l": 2 * long})
+    s = np.load(tmp_path / "a" / "s.npy")
+    la, lb = np.load(tmp_path / "a" / "l.npy"), np.load(tmp_path / "b" / "l.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, short)
+    assert la.dtype == np.float64 and la.shape == (bench.DUMP_SAMPLE,) and np.array_equal(lb, 2 * la)
+    assert np.all(np.diff(la) > 0)                 # distinct entries, in DOF order
 
 
 def test_compulsory_bytes_model_and_slab_workload():

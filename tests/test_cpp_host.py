@@ -10,7 +10,7 @@ import pytest
 
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import tag_box_boundary
-from util import Problem
+from util import Problem, gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "fenicsx-fus_amd", "fenicsxfus_amd")
@@ -42,8 +42,7 @@ def write_input(path, pr, tags, kind, nsteps, c, rho, delta, beta, f0, p0, s0, d
 
 
 def test_cpp_header_builds_and_fails_loudly_without_device(orc, exe, tmp_path):
-    import torch
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("device present: covered by the gpu test")
     pr = Problem(orc, (2, 2, 2), 2)
     nc = pr.mesh.num_cells

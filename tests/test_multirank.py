@@ -110,7 +110,9 @@ def _gloo_worker(rank, size, port, q):
 
 
 def test_two_ranks_gloo_cpu(orc):
-    import torch.multiprocessing as mp
+    # (the standard library's spawn context: torch stays out of THIS process, whose later GPU tests hold the HIP
+    # runtime through libfusmi)
+    import multiprocessing as mp
 
     ref, m_ref, u_ref, v_ref = single_rank_reference(orc)
     ctx = mp.get_context("spawn")

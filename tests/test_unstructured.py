@@ -1,8 +1,11 @@
 """Unstructured meshes: the reference's own Gmsh fixture (cpp/fenicsx-sf/tests/test_operators3d/
 mesh.xdmf, committed as data in tests/golden/ref_test_operators3d_mesh.npz) read by this
 repository's XDMF/HDF5 reader, the geometric tensor-dofmap builder, and the operators on it with the
-reference test's input recipe (main.cpp:60-67, 78-79, 85, 129)."""
+reference test's input recipe (main.cpp:60-67, 78-79, 85, 129).  The reference's XDMF/HDF5 files
+themselves are committed as tests/golden/<name>.xdmf and <name>.h5.gz."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -11,8 +14,17 @@ import fenicsxfus_amd as fa
 from fenicsxfus_amd.unstructured import VTK_TO_TENSOR, HexFunctionSpace, HexMesh, read_xdmf_hex_mesh
 from util import Problem
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "ref_test_operators3d_mesh.npz")
-REF_XDMF = "/root/reference/cpp/fenicsx-sf/tests/test_operators3d/mesh.xdmf"
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+GOLD = os.path.join(GOLDEN, "ref_test_operators3d_mesh.npz")
+
+
+def golden_xdmf(stem, directory):
+    """Unpack tests/golden/<stem>.xdmf and <stem>.h5.gz into ``directory`` under the names the XDMF
+    file refers to (mesh.xdmf, mesh.h5); returns the XDMF path."""
+    shutil.copyfile(os.path.join(GOLDEN, stem + ".xdmf"), os.path.join(directory, "mesh.xdmf"))
+    with gzip.open(os.path.join(GOLDEN, stem + ".h5.gz"), "rb") as src, open(os.path.join(directory, "mesh.h5"), "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    return os.path.join(directory, "mesh.xdmf")
 
 
 @pytest.fixture(scope="module")
@@ -23,10 +35,8 @@ def ref_mesh():
     return mesh, tags
 
 
-def test_xdmf_hdf5_reader_matches_fixture():
-    if not os.path.exists(REF_XDMF):
-        pytest.skip("reference tree absent")
-    mesh, cell_vals, tags = read_xdmf_hex_mesh(REF_XDMF)
+def test_xdmf_hdf5_reader_matches_fixture(tmp_path):
+    mesh, cell_vals, tags = read_xdmf_hex_mesh(golden_xdmf("ref_test_operators3d_mesh", tmp_path))
     g = np.load(GOLD)
     assert np.array_equal(mesh.geometry.x, g["geometry"])
     assert np.array_equal(mesh.geometry.dofmap, g["topology_vtk"][:, VTK_TO_TENSOR])
@@ -130,8 +140,7 @@ def test_point_evaluation(ref_mesh):
 
 
 # ---- the naive 2-D operator test's own quadrilateral mesh -------------------------------------------
-GOLD2 = os.path.join(os.path.dirname(__file__), "golden", "ref_test_operators2d_mesh.npz")
-REF_XDMF2 = "/root/reference/cpp/fenicsx-sf-naive/tests/test_operators2d/mesh_1/mesh.xdmf"
+GOLD2 = os.path.join(GOLDEN, "ref_test_operators2d_mesh.npz")
 
 
 @pytest.fixture(scope="module")
@@ -159,12 +168,11 @@ def _recipe2d(V, nc):
             ("stiffness", vn, full(-delta0 / rho0 / c0 / c0))]
 
 
-def test_reference_2d_mesh_reader_space_and_oracle_kats(orc, ref_mesh2d):
+def test_reference_2d_mesh_reader_space_and_oracle_kats(orc, ref_mesh2d, tmp_path):
     mesh, tags = ref_mesh2d
-    if os.path.exists(REF_XDMF2):
-        m2, cv, t2 = fa.read_xdmf_mesh(REF_XDMF2)
-        assert np.array_equal(m2.geometry.dofmap, mesh.geometry.dofmap) and np.array_equal(m2.geometry.x, mesh.geometry.x)
-        assert len(cv) == 265 and np.array_equal(t2.cells, tags.cells)
+    m2, cv, t2 = fa.read_xdmf_mesh(golden_xdmf("ref_test_operators2d_mesh", tmp_path))
+    assert np.array_equal(m2.geometry.dofmap, mesh.geometry.dofmap) and np.array_equal(m2.geometry.x, mesh.geometry.x)
+    assert len(cv) == 265 and np.array_equal(t2.cells, tags.cells)
     assert mesh.tdim == 2 and mesh.num_cells == 265 and mesh.entity_counts() == (296, 560, 0, 265)
     assert len(tags.cells) == 60                                 # every boundary edge is tagged
     V = HexFunctionSpace(mesh, 4)
@@ -255,8 +263,7 @@ def test_vtu_output_round_trip(ref_mesh2d, tmp_path, binary):
 
 
 # ---- second-order (9-node) quadrilaterals: the naive 2-D operator test's mesh_2 -----------------------
-GOLD2B = os.path.join(os.path.dirname(__file__), "golden", "ref_test_operators2d_mesh2.npz")
-REF_XDMF2B = "/root/reference/cpp/fenicsx-sf-naive/tests/test_operators2d/mesh_2/mesh.xdmf"
+GOLD2B = os.path.join(GOLDEN, "ref_test_operators2d_mesh2.npz")
 
 
 def _q2_mesh(curved=0.0, seed=0):
@@ -279,12 +286,11 @@ def _q2_mesh(curved=0.0, seed=0):
     return mesh, mesh.facet_tags(g["facet_topology"], g["facet_values"])
 
 
-def test_second_order_quads_reader_and_oracle(orc, ref_mesh2d):
+def test_second_order_quads_reader_and_oracle(orc, ref_mesh2d, tmp_path):
     mesh, tags = _q2_mesh()
-    if os.path.exists(REF_XDMF2B):
-        m2, cv, t2 = fa.read_xdmf_mesh(REF_XDMF2B)
-        assert m2.order == 2 and np.array_equal(m2.geometry.dofmap, mesh.geometry.dofmap)
-        assert len(cv) == 265 and np.array_equal(t2.cells, tags.cells)
+    m2, cv, t2 = fa.read_xdmf_mesh(golden_xdmf("ref_test_operators2d_mesh2", tmp_path))
+    assert m2.order == 2 and np.array_equal(m2.geometry.dofmap, mesh.geometry.dofmap)
+    assert len(cv) == 265 and np.array_equal(t2.cells, tags.cells)
     assert mesh.order == 2 and mesh.geometry.dofmap.shape == (265, 9) and len(tags.cells) == 60
     assert mesh.entity_counts() == (296, 560, 0, 265)
     V = HexFunctionSpace(mesh, 4)

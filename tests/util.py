@@ -1,7 +1,19 @@
 """Shared problem builders for the tests (inputs follow SURVEY 8d / the reference tests' recipes)."""
+import functools
+import subprocess
+import sys
+
 import numpy as np
 
 from fenicsxfus_amd import BoxMesh, FunctionSpace, FacetTags
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_present() -> bool:
+    """torch.cuda.is_available(), asked in a child interpreter: torch's HIP runtime must not be loaded into a test
+    process that holds libfusmi's (the in-process GPU tests then find no device)."""
+    return subprocess.run([sys.executable, "-c", "import sys, torch; sys.exit(0 if torch.cuda.is_available() else 1)"],
+                          capture_output=True).returncode == 0
 
 
 class Problem:

@@ -9,4 +9,4 @@ for geom in trilinear auto; do
   tools/ab_matrix.sh ${out}_p6_$geom 1 "--dtype f32 --P 6 --geometry $geom" -- $lib -- "--block-elems 4" "--block-elems 8" "--block-elems 12" "--block-elems 16"
   tools/ab_matrix.sh ${out}_p7_$geom 1 "--dtype f32 --P 7 --geometry $geom" -- $lib -- "--block-elems 4" "--block-elems 8" "--block-elems 12" "--block-elems 16"
 done
-cat gpurun_out/${out}_p*_*.txt > gpurun_out/${out}_all.txt
+cat ${OUT_DIR:-results}/${out}_p*_*.txt > ${OUT_DIR:-results}/${out}_all.txt

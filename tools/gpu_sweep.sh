@@ -1,12 +1,14 @@
 #!/bin/bash
 # usage: gpu_sweep.sh <out.txt>   (through gpurun) -- one bench line per degree / precision / model at 64^3
-out=gpurun_out/$1
+outdir=${OUT_DIR:-results}
+mkdir -p $outdir
+out=$outdir/$1
 : > $out
 run() {
-  timeout -k 10 400 python bench.py --no-cpu --traffic none --both-geometries 0 --repeats 3 $@ > gpurun_out/sweep_tmp.json 2>> gpurun_out/sweep.err \
-    && python - "$*" >> $out <<'PY'
+  timeout -k 10 400 python bench.py --full --no-cpu --traffic none --both-geometries 0 --repeats 3 $@ > $outdir/sweep_tmp.json 2>> $outdir/sweep.err \
+    && python - "$*" "$outdir/sweep_tmp.json" >> $out <<'PY'
 import json,sys
-d=json.load(open("gpurun_out/sweep_tmp.json"))
+d=json.load(open(sys.argv[2]))
 r=d["roofline"]
 print("%-46s %.4g DOF-upd/s  %.4f ms/step  kernel %.4f ms  frac(8d) %.3f  frac_compulsory %.3f  step frac_compulsory %.3f  pk=%s blocks=%d lds=%d" % (sys.argv[1], d["value"], d["ms_per_step"], r["avg_launch_ms"], r["frac"], r["frac_compulsory"], d["step_roofline"]["frac_compulsory"], d["config"]["packed_fp32"], d["config"]["blocks"], d["config"]["lds_bytes_per_block"]))
 PY
