@@ -10,7 +10,7 @@ import pytest
 import fenicsxfus_amd as fa
 from fake_dolfinx import FakeBasix, exchange_all, partition
 from fenicsxfus_amd import dolfinx_adapter as ad
-from util import Problem
+from util import Problem, assert_live, layer_and_face_regions, live_state
 
 F0, P0, S0 = 0.5e6, 60000.0, 1500.0
 
@@ -82,7 +82,7 @@ def test_single_rank_space_has_no_neighbours(orc):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("endpoints_first", [False, True])
-def test_four_ranks_through_the_adapter_gpu(orc, endpoints_first):
+def test_four_ranks_through_the_adapter_gpu(orc, endpoints_first, start="rest"):
     """Linear RK4 on four quadrant ranks whose spaces come from `wrap_function_space`: operator action and
     5 steps against the single-rank oracle, results in each rank's DOLFINx-local numbering, DOFs held by all
     four ranks bit-identical on every one of them."""
@@ -95,9 +95,14 @@ def test_four_ranks_through_the_adapter_gpu(orc, endpoints_first):
     gtags = fa.tag_box_boundary(pr.mesh)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, gtags)
     dt = 0.4 * (hi[0] / n[0]) / (2800.0 * P**2)
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    u0, v0 = live_state(pr, 6, P0, F0) if start == "live" else (np.zeros(pr.ndofs), np.zeros(pr.ndofs))
+    u, v = u0.copy(), v0.copy()
     orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, P0, S0, 0.0, nsteps * dt * (1 + 1e-12), dt, u, v)
     assert np.abs(u).max() > 0
+    if start == "live":      # every interface (the DOFs two or more ranks hold) carries the state
+        ids = [rk["oracle_ids"] for rk in ranks]
+        planes = {f"if{a}|{b}": np.intersect1d(ids[a], ids[b]) for a in range(len(ids)) for b in range(a + 1, len(ids))}
+        assert_live((u, v), {**layer_and_face_regions(pr), **planes})
     # single-rank operator action through a wrapped space (rank-local part: every cell of that rank)
     x = np.random.default_rng(0).standard_normal(pr.ndofs)
     yref = pr.K(x, coeff)
@@ -119,8 +124,10 @@ def test_four_ranks_through_the_adapter_gpu(orc, endpoints_first):
         np.add.at(ysum, ids, yl)                      # the ranks' partial actions add up to the global one
     assert np.abs(ysum - yref).max() < 1e-12 * np.abs(yref).max()
     fa.group_finish_setup(mods)
-    for mdl in mods:
+    for rk, mdl in zip(ranks, mods):
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[rk["oracle_ids"]], v0[rk["oracle_ids"]])
     fa.group_rk4_steps(mods, 0.0, dt, nsteps)
     sols = []
     for rk, mdl in zip(ranks, mods):
@@ -137,3 +144,10 @@ def test_four_ranks_through_the_adapter_gpu(orc, endpoints_first):
         mdl.close()
     for cx in ctxs:
         cx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("endpoints_first", [False, True])
+def test_four_ranks_through_the_adapter_live_gpu(orc, endpoints_first):
+    """test_four_ranks_through_the_adapter_gpu from a live start."""
+    test_four_ranks_through_the_adapter_gpu(orc, endpoints_first, start="live")

@@ -10,7 +10,7 @@ import pytest
 
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import tag_box_boundary
-from util import Problem
+from util import Problem, assert_live, layer_and_face_regions, live_state, slab_interface_regions
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +29,12 @@ def _materials(mesh, L):
     return np.where(sel, 2800.0, 1500.0), np.where(sel, 1850.0, 1000.0)
 
 
-def _oracle_rk4(orc, pr, c, rho, tags, dt, nsteps, dtype):
+def _oracle_rk4(orc, pr, c, rho, tags, dt, nsteps, dtype, start=None):
     m, src, absb, coeff = pr.linear_model_vectors(c.astype(dtype), rho.astype(dtype), tags)
-    u, v = np.zeros(pr.ndofs, dtype), np.zeros(pr.ndofs, dtype)
+    if start is None:
+        u, v = np.zeros(pr.ndofs, dtype), np.zeros(pr.ndofs, dtype)
+    else:
+        u, v = (np.array(a, dtype=dtype) for a in start)
     ns = orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, P0, S0, 0.0, nsteps * dt * (1 - 1e-6), dt,
                         u, v, dtype=dtype)
     assert ns == nsteps
@@ -66,7 +69,7 @@ def test_fp32_linear_rk4_vs_float_and_double_oracle(orc, P, n, perturb, mode):
 
 
 @pytest.mark.parametrize("P,n", [(6, (6, 3, 3)), (4, (8, 4, 4))])
-def test_fp32_two_slabs_in_process(orc, P, n):
+def test_fp32_two_slabs_in_process(orc, P, n, start="rest"):
     """configs[4]'s partition in small: two x-slabs in fp32 through the library's pack / ordered-sum /
     stage kernels (in-process transport) against the single-rank float and double oracles; the
     interface plane is bit-identical on both sharers."""
@@ -77,9 +80,12 @@ def test_fp32_two_slabs_in_process(orc, P, n):
     c, rho = _materials(pr64.mesh, L[0])
     tags = tag_box_boundary(pr64.mesh)
     dt = 0.5 * (L[0] / n[0]) / (c.max() * P**2)
-    u32, v32 = _oracle_rk4(orc, pr32, c, rho, tags, dt, nsteps, np.float32)
-    u64, v64 = _oracle_rk4(orc, pr64, c, rho, tags, dt, nsteps, np.float64)
     size = 2
+    u0, v0 = live_state(pr64, 5, P0, F0) if start == "live" else (None, None)
+    u32, v32 = _oracle_rk4(orc, pr32, c, rho, tags, dt, nsteps, np.float32, None if u0 is None else (u0, v0))
+    u64, v64 = _oracle_rk4(orc, pr64, c, rho, tags, dt, nsteps, np.float64, None if u0 is None else (u0, v0))
+    if start == "live":
+        assert_live((u64, v64), {**layer_and_face_regions(pr64), **slab_interface_regions(pr64, size)})
     ctxs = [fa.Context(0) for _ in range(size)]
     fa.Context.init_local_group(ctxs)
     models, offs = [], []
@@ -92,8 +98,10 @@ def test_fp32_two_slabs_in_process(orc, P, n):
         assert models[-1].data.geometry_mode() == "trilinear"
         offs.append(V.global_offset)
     fa.group_finish_setup(models)
-    for m in models:
+    for m, off in zip(models, offs):
         m.init()
+        if start == "live":
+            m.set_state(u0[off:off + m.data.ndofs], v0[off:off + m.data.ndofs])
     fa.group_rk4_steps(models, 0.0, dt, nsteps)
     us = []
     for r, mdl in enumerate(models):
@@ -108,6 +116,12 @@ def test_fp32_two_slabs_in_process(orc, P, n):
         mdl.close()
     for cx in ctxs:
         cx.close()
+
+
+@pytest.mark.parametrize("P,n", [(6, (6, 3, 3)), (4, (8, 4, 4))])
+def test_fp32_two_slabs_in_process_live(orc, P, n):
+    """test_fp32_two_slabs_in_process from a live start."""
+    test_fp32_two_slabs_in_process(orc, P, n, start="live")
 
 
 def _full_size_properties(geometry, P, ncell, L, dtype=np.float64, tol_sym=1e-10, tol_one=1e-11):

@@ -7,7 +7,7 @@ import pytest
 
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import tag_box_boundary
-from util import Problem
+from util import Problem, assert_live, layer_and_face_regions, live_state, slab_interface_regions
 
 pytestmark = pytest.mark.gpu
 
@@ -212,7 +212,7 @@ def test_quad_lossy_and_westervelt_vs_oracle(orc, ctx):
 
 
 @pytest.mark.parametrize("size", [2, 3])
-def test_quad_slabs_in_process(orc, size):
+def test_quad_slabs_in_process(orc, size, start="rest"):
     """x-slab partition of a quadrilateral mesh over `size` contexts on one GPU (in-process
     transport): same state as the single-rank oracle, interface lines bit-identical."""
     L, P, n = [0.024, 0.012], 4, (9, 5)
@@ -223,8 +223,11 @@ def test_quad_slabs_in_process(orc, size):
     c, rho = np.full(nc, 1500.0), np.full(nc, 1000.0)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, tags)
     dt = 0.5 * (L[0] / n[0]) / (1500.0 * P**2)
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    u0, v0 = live_state(pr, 4, p0, f0) if start == "live" else (np.zeros(pr.ndofs), np.zeros(pr.ndofs))
+    u, v = u0.copy(), v0.copy()
     orc.linear_rk4(2, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, f0, p0, s0, 0.0, nsteps * dt * (1 + 1e-12), dt, u, v)
+    if start == "live":
+        assert_live((u, v), {**layer_and_face_regions(pr), **slab_interface_regions(pr, size)})
     ctxs = [fa.Context(0) for _ in range(size)]
     fa.Context.init_local_group(ctxs)
     models, offs = [], []
@@ -236,8 +239,10 @@ def test_quad_slabs_in_process(orc, size):
                                                 f0, p0, s0, 4, dt, V=V, ctx=ctxs[r]))
         offs.append(V.global_offset)
     fa.group_finish_setup(models)
-    for mdl in models:
+    for mdl, off in zip(models, offs):
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[off:off + mdl.data.ndofs], v0[off:off + mdl.data.ndofs])
     fa.group_rk4_steps(models, 0.0, dt, nsteps)
     us = []
     for r, mdl in enumerate(models):
@@ -245,6 +250,8 @@ def test_quad_slabs_in_process(orc, size):
         ur = mdl.u_sol().x.array
         us.append(ur)
         assert np.abs(ur - u[offs[r]:offs[r] + k]).max() < 1e-10 * np.abs(u).max()
+        if start == "live":
+            assert np.abs(mdl.v_n.x.array - v[offs[r]:offs[r] + k]).max() < 1e-10 * np.abs(v).max()
     for r in range(size - 1):
         line = len(us[r]) - (offs[r + 1] - offs[r])
         assert np.array_equal(us[r][-line:], us[r + 1][:line])
@@ -252,3 +259,9 @@ def test_quad_slabs_in_process(orc, size):
         mdl.close()
     for cx in ctxs:
         cx.close()
+
+
+@pytest.mark.parametrize("size", [2, 3])
+def test_quad_slabs_in_process_live(orc, size):
+    """test_quad_slabs_in_process from a live start."""
+    test_quad_slabs_in_process(orc, size, start="live")

@@ -10,11 +10,27 @@ import numpy as np
 import pytest
 
 import fenicsxfus_amd as fa
-from util import Problem
+from util import Problem, assert_live, layer_and_face_regions, live_state, slab_interface_regions
 
 P, N_GLOBAL, HI = 4, (6, 3, 3), [0.024, 0.012, 0.012]
 F0, P0, S0 = 0.5e6, 60000.0, 1500.0
 NSTEPS = 6
+SEED = 3
+STARTS = ["rest", "live"]
+
+
+def start_state(pr, start, amp=P0):
+    """(u0, v0) on the global problem: zeros, or a live state (u ~ amp on every DOF, see util.live_state)."""
+    if start == "rest":
+        return np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    return live_state(pr, SEED, amp, F0)
+
+
+def check_live(pr, start, ref, size):
+    """From a live start: the reference carries >= 1e-2 of its max in every element layer, on every boundary face
+    and on every interface plane of the ``size`` slabs."""
+    if start == "live":
+        assert_live(ref, {**layer_and_face_regions(pr), **slab_interface_regions(pr, size)})
 
 
 def material(mesh):
@@ -30,12 +46,16 @@ def dt_value():
     return 0.5 * (HI[0] / N_GLOBAL[0]) / (2800.0 * P**2)
 
 
-def single_rank_reference(orc):
+def single_rank_reference(orc, start="rest", mass_scale=None):
+    """The single-rank oracle run of the slab tests' problem; ``mass_scale`` = (dof mask, factor) changes the lumped
+    mass there (the CPU guards)."""
     pr = Problem(orc, N_GLOBAL, P, hi=HI, perturb=0.1)
     c, rho = material(pr.mesh)
     tags = fa.tag_box_boundary(pr.mesh)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, tags)
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    if mass_scale is not None:
+        m = np.where(mass_scale[0], m * mass_scale[1], m)
+    u, v = start_state(pr, start)
     dt = dt_value()
     # tf a hair past NSTEPS*dt: NSTEPS full steps (+ a ~1e-12*dt remainder step, far below tolerance)
     orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, P0, S0, 0.0, NSTEPS * dt * (1 + 1e-12), dt, u, v)
@@ -69,7 +89,7 @@ def _exchange_sum(dist, rank, V, vec):
     return out
 
 
-def _gloo_worker(rank, size, port, q):
+def _gloo_worker(rank, size, port, q, start="rest"):
     import torch.distributed as dist
 
     import oracle as orc
@@ -83,7 +103,9 @@ def _gloo_worker(rank, size, port, q):
     m, src, absb = (_exchange_sum(dist, rank, pr.V, a) for a in (m, src, absb))
     # host restatement of the library's stage loop (fusmi.hip stage_begin / stage_end)
     n = pr.ndofs
-    u0, v0 = np.zeros(n), np.zeros(n)
+    off = pr.V.global_offset
+    ug, vg = start_state(Problem(orc, N_GLOBAL, P, hi=HI, perturb=0.1), start)
+    u0, v0 = ug[off:off + n].copy(), vg[off:off + n].copy()
     u_, v_, un, vn = (np.zeros(n) for _ in range(4))
     dt, t = dt_value(), 0.0
     a_r, b_r, c_r = [0, .5, .5, 1, 0], [1 / 6, 1 / 3, 1 / 3, 1 / 6], [0, .5, .5, 1]
@@ -109,16 +131,17 @@ def _gloo_worker(rank, size, port, q):
     dist.destroy_process_group()
 
 
-def test_two_ranks_gloo_cpu(orc):
+def test_two_ranks_gloo_cpu(orc, start="rest"):
     # (the standard library's spawn context: torch stays out of THIS process, whose later GPU tests hold the HIP
     # runtime through libfusmi)
     import multiprocessing as mp
 
-    ref, m_ref, u_ref, v_ref = single_rank_reference(orc)
+    ref, m_ref, u_ref, v_ref = single_rank_reference(orc, start)
+    check_live(ref, start, (u_ref, v_ref), 2)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_gloo_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_gloo_worker, args=(r, 2, port, q, start)) for r in range(2)]
     [p.start() for p in procs]
     res = [q.get(timeout=120) for _ in procs]
     [p.join(timeout=60) for p in procs]
@@ -136,11 +159,19 @@ def test_two_ranks_gloo_cpu(orc):
     assert np.array_equal(planes[0][1][off1:], planes[1][1][:plane])
 
 
+def test_two_ranks_gloo_live_cpu(orc):
+    """test_two_ranks_gloo_cpu from a live start: the host restatement of the stage loop exchanges interface values
+    of the size of the state."""
+    test_two_ranks_gloo_cpu(orc, start="live")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("geometry", ["stream", None])   # streamed G / default (G recomputed from the cell maps)
 @pytest.mark.parametrize("size", [2, 3])
-def test_slabs_in_process_gpu(orc, size, geometry):
-    ref, m_ref, u_ref, v_ref = single_rank_reference(orc)
+def test_slabs_in_process_gpu(orc, size, geometry, start="rest"):
+    ref, m_ref, u_ref, v_ref = single_rank_reference(orc, start)
+    check_live(ref, start, (u_ref, v_ref), size)
+    u0, v0 = start_state(ref, start)
     ctxs = [fa.Context(0, geometry=geometry) for _ in range(size)]
     fa.Context.init_local_group(ctxs)
     models, offs = [], []
@@ -153,8 +184,10 @@ def test_slabs_in_process_gpu(orc, size, geometry):
                                                 ctx=ctxs[r]))
         offs.append(V.global_offset)
     fa.group_finish_setup(models)
-    for m in models:
+    for m, off in zip(models, offs):
         m.init()
+        if start == "live":
+            m.set_state(u0[off:off + m.data.ndofs], v0[off:off + m.data.ndofs])
     fa.group_rk4_steps(models, 0.0, dt, NSTEPS)
     us = []
     for r, mdl in enumerate(models):
@@ -181,8 +214,16 @@ def test_slabs_in_process_gpu(orc, size, geometry):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("geometry", ["stream", None])
+@pytest.mark.parametrize("size", [2, 3])
+def test_slabs_in_process_live_gpu(orc, size, geometry):
+    """test_slabs_in_process_gpu from a live start: every interface plane carries the state at every stage."""
+    test_slabs_in_process_gpu(orc, size, geometry, start="live")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("overlap", [0, 1])
-def test_slabs_overlap_blocks_option_gpu(orc, overlap):
+def test_slabs_overlap_blocks_option_gpu(orc, overlap, start="rest"):
     """Option "overlap_blocks": interface blocks launched first, the remaining blocks after the pack.
     Elongated box so that the 1 x 2 x 2 blocks next to the cut are a strict subset of each rank's
     blocks; both settings must give the single-rank oracle's state."""
@@ -192,8 +233,10 @@ def test_slabs_overlap_blocks_option_gpu(orc, overlap):
     c, rho = np.full(nc, 1500.0), np.full(nc, 1000.0)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, fa.tag_box_boundary(pr.mesh))
     dt = 0.5 * (hi[0] / n[0]) / (1500.0 * P**2)
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    u0, v0 = start_state(pr, start)
+    u, v = u0.copy(), v0.copy()
     orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, P0, S0, 0.0, nsteps * dt * (1 + 1e-12), dt, u, v)
+    check_live(pr, start, (u, v), size)
     ctxs = [fa.Context(0, block_elems=4) for _ in range(size)]
     for cx in ctxs:
         cx.set_option("overlap_blocks", overlap)
@@ -208,8 +251,10 @@ def test_slabs_overlap_blocks_option_gpu(orc, overlap):
         assert models[-1].data.info()["nblocks"] == 6
         offs.append(V.global_offset)
     fa.group_finish_setup(models)
-    for mdl in models:
+    for mdl, off in zip(models, offs):
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[off:off + mdl.data.ndofs], v0[off:off + mdl.data.ndofs])
     fa.group_rk4_steps(models, 0.0, dt, nsteps)
     for r, mdl in enumerate(models):
         k = mdl.data.ndofs
@@ -223,7 +268,14 @@ def test_slabs_overlap_blocks_option_gpu(orc, overlap):
 
 
 @pytest.mark.gpu
-def test_westervelt_slabs_in_process_gpu(orc):
+@pytest.mark.parametrize("overlap", [0, 1])
+def test_slabs_overlap_blocks_option_live_gpu(orc, overlap):
+    """test_slabs_overlap_blocks_option_gpu from a live start."""
+    test_slabs_overlap_blocks_option_gpu(orc, overlap, start="live")
+
+
+@pytest.mark.gpu
+def test_westervelt_slabs_in_process_gpu(orc, start="rest"):
     # the nonlinear model across 2 slabs: m0 and the M(nlin1) diagonal are summed over the sharers
     pr = Problem(orc, N_GLOBAL, P, hi=HI, perturb=0.1)
     c, rho = material(pr.mesh)
@@ -232,12 +284,14 @@ def test_westervelt_slabs_in_process_gpu(orc):
     delta, beta = fa.compute_diffusivity_of_sound(w0, 1500.0, 0.2), 3.5
     m, src, absb, src2, lin, att = pr.lossy_model_vectors(c, rho, delta, tags)
     n1 = -2.0 * beta / rho**2 / c**4
-    u_ref, v_ref = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
     dt = dt_value()
     p0 = 6.0e6
+    u0, v0 = start_state(pr, start, p0)
+    u_ref, v_ref = u0.copy(), v0.copy()
     orc.westervelt_rk4(3, pr.N, pr.dm, pr.G, pr.detJ, pr.D, lin, att, n1, -n1, m, src, absb, src2, F0, p0, S0, 0.0,
                        NSTEPS * dt * (1 + 1e-12), dt, u_ref, v_ref)
     size = 2
+    check_live(pr, start, (u_ref, v_ref), size)
     ctxs = [fa.Context(0) for _ in range(size)]
     fa.Context.init_local_group(ctxs)
     models, offs = [], []
@@ -250,16 +304,27 @@ def test_westervelt_slabs_in_process_gpu(orc):
                                                     np.full(nc, beta), F0, p0, S0, 4, dt, V=V, ctx=ctxs[r]))
         offs.append(V.global_offset)
     fa.group_finish_setup(models)
-    for mdl in models:
+    for mdl, off in zip(models, offs):
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[off:off + mdl.data.ndofs], v0[off:off + mdl.data.ndofs])
     fa.group_rk4_steps(models, 0.0, dt, NSTEPS)
     for r, mdl in enumerate(models):
         n = mdl.data.ndofs
         u = mdl.u_sol().x.array
         assert np.abs(u - u_ref[offs[r]:offs[r] + n]).max() < 1e-10 * np.abs(u_ref).max()
+        if start == "live":
+            assert np.abs(mdl.v_n.x.array - v_ref[offs[r]:offs[r] + n]).max() < 1e-10 * np.abs(v_ref).max()
         mdl.close()
     for cx in ctxs:
         cx.close()
+
+
+@pytest.mark.gpu
+def test_westervelt_slabs_in_process_live_gpu(orc):
+    """test_westervelt_slabs_in_process_gpu from a live start (u ~ 6 MPa on every DOF: the nonlinear mass terms
+    matter at the interface too)."""
+    test_westervelt_slabs_in_process_gpu(orc, start="live")
 
 
 @pytest.mark.gpu
@@ -271,7 +336,7 @@ def test_rccl_binding_selftest():
 
 
 @pytest.mark.gpu
-def test_general_partition_four_quadrants_gpu(orc):
+def test_general_partition_four_quadrants_gpu(orc, start="rest"):
     """A partition DOLFINx could produce rather than slabs: the box cut into 2 x 2 quadrants in x-y,
     every rank an unstructured local mesh with its own (geometric) DOF numbering, neighbour lists
     built from global DOF identity and ordered by it.  Interface faces are not contiguous index
@@ -287,7 +352,8 @@ def test_general_partition_four_quadrants_gpu(orc):
     gtags = fa.tag_box_boundary(pr.mesh)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, gtags)
     dt = 0.4 * (hi[0] / n[0]) / (2800.0 * Pq**2)
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
+    u0, v0 = start_state(pr, start)
+    u, v = u0.copy(), v0.copy()
     orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, P0, S0, 0.0, nsteps * dt * (1 + 1e-12), dt, u, v)
     assert np.abs(u).max() > 0
     from scipy.spatial import cKDTree
@@ -330,11 +396,16 @@ def test_general_partition_four_quadrants_gpu(orc):
         assert len(V.neighbours) == 3                     # every quadrant touches the central line
     four = set(gids[0]) & set(gids[1]) & set(gids[2]) & set(gids[3])
     assert len(four) == n[2] * Pq + 1                     # dofs held by all four ranks
+    if start == "live":      # every interface (the DOFs two or more quadrants hold) carries the state
+        planes = {f"if{r}|{q}": np.intersect1d(gids[r], gids[q]) for r in range(size) for q in range(r + 1, size)}
+        assert_live((u, v), {**layer_and_face_regions(pr), **planes})
     mods = [fa.LinearSpectralExplicit(lm, tg, Pq, cr, rr, F0, P0, S0, 4, dt, V=V, ctx=ctxs[r])
             for r, (lm, V, tg, cr, rr) in enumerate(models)]
     fa.group_finish_setup(mods)
-    for mdl in mods:
+    for mdl, g in zip(mods, gids):
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[g], v0[g])
     fa.group_rk4_steps(mods, 0.0, dt, nsteps)
     sols = []
     for r, mdl in enumerate(mods):
@@ -352,8 +423,14 @@ def test_general_partition_four_quadrants_gpu(orc):
 
 
 @pytest.mark.gpu
+def test_general_partition_four_quadrants_live_gpu(orc):
+    """test_general_partition_four_quadrants_gpu from a live start."""
+    test_general_partition_four_quadrants_gpu(orc, start="live")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("model_kind", ["linear", "westervelt"])
-def test_external_transport_gpu(orc, model_kind):
+def test_external_transport_gpu(orc, model_kind, start="rest"):
     """The external-transport entry points (what a GPU-aware-MPI caller uses instead of the built-in
     RCCL exchange): three slab ranks on one GPU, the exchange done HERE by device-to-device copies
     between the ranks' send / receive buffers, the stage and setup halves driven one by one."""
@@ -365,11 +442,12 @@ def test_external_transport_gpu(orc, model_kind):
     c, rho = material(pr.mesh)
     gt = fa.tag_box_boundary(pr.mesh)
     dt = dt_value()
-    u, v = np.zeros(pr.ndofs), np.zeros(pr.ndofs)
     w0 = 2 * np.pi * F0
     delta = np.where(c > 2000.0, fa.compute_diffusivity_of_sound(w0, 2800.0, 46.0), fa.compute_diffusivity_of_sound(w0, 1500.0, 0.2))
     beta = np.where(c > 2000.0, 6.0, 3.5)
     p0 = P0 if model_kind == "linear" else 100 * P0
+    u0, v0 = start_state(pr, start, p0)
+    u, v = u0.copy(), v0.copy()
     if model_kind == "linear":
         m, src, absb, coeff = pr.linear_model_vectors(c, rho, gt)
         orc.linear_rk4(3, pr.N, pr.dm, pr.G, pr.D, coeff, m, src, absb, F0, p0, S0, 0.0, nsteps * dt * (1 + 1e-12), dt, u, v)
@@ -413,9 +491,12 @@ def test_external_transport_gpu(orc, model_kind):
         exchange()
         for mdl in models:
             mdl.setup_unpack(k)
-    for mdl in models:
+    check_live(pr, start, (u, v), size)
+    for mdl, off in zip(models, offs):
         mdl.setup_finish()
         mdl.init()
+        if start == "live":
+            mdl.set_state(u0[off:off + mdl.data.ndofs], v0[off:off + mdl.data.ndofs])
     t = 0.0
     for _ in range(nsteps):
         for i in range(4):
@@ -437,6 +518,13 @@ def test_external_transport_gpu(orc, model_kind):
         mdl.close()
     for cx in ctxs:
         cx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model_kind", ["linear", "westervelt"])
+def test_external_transport_live_gpu(orc, model_kind):
+    """test_external_transport_gpu from a live start."""
+    test_external_transport_gpu(orc, model_kind, start="live")
 
 
 @pytest.mark.gpu
@@ -478,7 +566,7 @@ def test_slabs_higher_degree_gpu(orc, Ph):
         cx.close()
 
 
-def _gpu_rank_worker(rank, size, port, q):
+def _gpu_rank_worker(rank, size, port, q, start="rest"):
     """One RANK PROCESS of the N > 1 path on the HIP library: its own x-slab, the library's pack / ordered-sum / stage
     kernels, interface values moved between the processes by gloo through host memory (the external-transport entry
     points of fusmi.h; on a multi-GPU node the library's RCCL send/recv takes this place)."""
@@ -518,6 +606,12 @@ def _gpu_rank_worker(rank, size, port, q):
 
     mdl.external_setup(exchange)
     mdl.init()
+    if start == "live":
+        import oracle as orc
+
+        ug, vg = start_state(Problem(orc, N_GLOBAL, P, hi=HI, perturb=0.1), start)
+        off, k = V.global_offset, mdl.data.ndofs
+        mdl.set_state(ug[off:off + k], vg[off:off + k])
     mdl.external_rk_steps(0.0, dt, NSTEPS, exchange)
     q.put((rank, V.global_offset, mdl.mass_vector(), mdl.u_sol().x.array.copy(), mdl.v_n.x.array.copy()))
     dist.barrier()
@@ -528,18 +622,19 @@ def _gpu_rank_worker(rank, size, port, q):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("size", [2, 3])
-def test_distinct_rank_processes_gpu(orc, size):
+def test_distinct_rank_processes_gpu(orc, size, start="rest"):
     """Two / three distinct rank PROCESSES on the HIP path (they share this box's one GPU; gloo moves the interface
     values): state equal to the single-rank oracle, interface planes bit-identical on both sharers."""
     # (no torch in THIS process: it holds the HIP runtime through libfusmi already; the rank processes are fresh
     # interpreters that import torch first)
     import multiprocessing as mp
 
-    ref, m_ref, u_ref, v_ref = single_rank_reference(orc)
+    ref, m_ref, u_ref, v_ref = single_rank_reference(orc, start)
+    check_live(ref, start, (u_ref, v_ref), size)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_gpu_rank_worker, args=(r, size, port, q)) for r in range(size)]
+    procs = [ctx.Process(target=_gpu_rank_worker, args=(r, size, port, q, start)) for r in range(size)]
     [p.start() for p in procs]
     res = sorted((q.get(timeout=600) for _ in procs), key=lambda t: t[0])
     [p.join(timeout=120) for p in procs]
@@ -552,3 +647,9 @@ def test_distinct_rank_processes_gpu(orc, size):
     for a, b in zip(res[:-1], res[1:]):
         plane = len(a[3]) - (b[1] - a[1])
         assert plane > 0 and np.array_equal(a[3][-plane:], b[3][:plane])
+
+
+@pytest.mark.gpu
+def test_distinct_rank_processes_live_gpu(orc):
+    """test_distinct_rank_processes_gpu from a live start, two rank processes."""
+    test_distinct_rank_processes_gpu(orc, 2, start="live")

@@ -77,3 +77,61 @@ class Problem:
         absb = self.facet_diag(allf, 7, 1.0 / (rho0 * c0))
         src2 = self.facet_diag(tags, 1, d0 / (rho0 * c0 * c0))
         return m, src, absb, src2, (-1.0 / rho0).astype(self.dtype), (-d0 / (rho0 * c0 * c0)).astype(self.dtype)
+
+
+# ---- live starts: every DOF of the compared state carries an O(1) value ---------------------------------------
+def live_state(pr, seed, amp, f0=0.5e6):
+    """(u0, v0) on the DOFs of the GLOBAL problem ``pr``: a few low-order cosine modes with random phases over the
+    box plus 1 % seeded per-DOF noise, u ~ amp and v ~ 2 pi f0 amp, in the problem's dtype.  A rank takes its part
+    by global offset (slabs) or by its global DOF ids, so sharers get identical values."""
+    X = pr.V.tabulate_dof_coordinates()[:, :pr.tdim].astype(np.float64)
+    lo, hi = X.min(axis=0), X.max(axis=0)
+    xn = (X - lo) / np.where(hi > lo, hi - lo, 1.0)
+    rng = np.random.default_rng(seed)
+    out = []
+    for scale in (amp, 2 * np.pi * f0 * amp):
+        f = np.ones(len(X))
+        for _ in range(4):
+            k = rng.integers(0, 3, pr.tdim)
+            f += rng.uniform(0.2, 0.5) * np.cos(np.pi * (xn @ k) + rng.uniform(0.0, 2 * np.pi))
+        f += 0.01 * rng.standard_normal(len(X))
+        out.append(np.ascontiguousarray(scale * f, dtype=pr.dtype))
+    return out[0], out[1]
+
+
+def layer_and_face_regions(pr):
+    """Global DOF ids of every element layer along x and of each of the 2 tdim boundary faces of the box."""
+    mesh = pr.mesh
+    layer = mesh._cidx[0] + mesh.cx0
+    regions = {f"layer{i}": np.unique(pr.dm[layer == i]) for i in range(mesh.n[0])}
+    cells, lf, ax, sd = mesh.exterior_facets()
+    for a in range(pr.tdim):
+        for s in (0, 1):
+            sel = (ax == a) & (sd == s)
+            tags = FacetTags(cells[sel], lf[sel], np.ones(int(sel.sum()), np.int32))
+            w = pr.facet_diag(tags, 1, np.ones(mesh.num_cells, pr.dtype))
+            regions[f"face{'xyz'[a]}{'-+'[s]}"] = np.flatnonzero(w)
+    return regions
+
+
+def slab_interface_regions(pr, size):
+    """Global DOF ids of the interface planes of ``size`` x-slabs of ``pr``'s box (what two slabs share)."""
+    out = {}
+    for r in range(1, size):
+        mesh = BoxMesh(pr.mesh.lo, pr.mesh.hi, pr.mesh.n, rank=r, size=size)
+        V = FunctionSpace(mesh, pr.P)
+        nb, idx = V.neighbours[0]
+        assert nb == r - 1
+        out[f"cut{r - 1}|{r}"] = V.global_offset + idx.astype(np.int64)
+    return out
+
+
+def assert_live(ref, regions, floor=1e-2):
+    """Precondition of a comparison with the oracle: every named region of the reference state carries at least
+    ``floor`` of its max, so that a comparison at a relative tolerance checks that region at all."""
+    for a in (ref if isinstance(ref, (tuple, list)) else (ref,)):
+        a = np.abs(np.asarray(a, dtype=np.float64))
+        top = a.max()
+        assert np.isfinite(top) and top > 0
+        weak = {k: float(a[idx].max() / top) for k, idx in regions.items() if len(idx) == 0 or a[idx].max() < floor * top}
+        assert not weak, f"reference state below {floor} of its max in {weak}"
