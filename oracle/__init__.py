@@ -166,43 +166,52 @@ def facet_diag(tdim, facet_cell, facet_local, cellcoef, xg, xdofmap, pts, wts, t
     return out
 
 
+def _steps(steps):
+    assert steps is None or steps >= 0
+    return C.c_int64(-1 if steps is None else int(steps))
+
+
 def linear_rk4(tdim, N, tensor_dofmap, G, D, coeff, m, src, absb, freq, p0, s0, t0, tf, dt, u, v,
-               dtype=np.float64, fast=False, order=4):
+               dtype=np.float64, fast=False, order=4, steps=None):
     """Linear.hpp rk4 restated (order 1-3: the Python reference's other RK tables); u, v updated in
-    place; returns the number of steps taken."""
+    place; returns the number of steps taken.  ``steps``: run exactly that many full steps of dt (tf ignored),
+    the loop time kept in double -- see oracle.h; None: the reference's tf-driven loop."""
     dm = _arr(tensor_dofmap, np.int32)
-    fn = getattr(lib(fast), "orc_linear_rk_" + _suf(dtype))
+    fn = getattr(lib(fast), "orc_linear_rk_n_" + _suf(dtype))
     fn.restype = C.c_int64
     assert u.flags.c_contiguous and v.flags.c_contiguous
     return fn(
         C.c_int(order), C.c_int(tdim), C.c_int64(dm.shape[0]), C.c_int64(len(u)), C.c_int(N), _p(dm), _p(_arr(G, dtype)),
         _p(_arr(D, dtype)), _p(_arr(coeff, dtype)), _p(_arr(m, dtype)), _p(_arr(src, dtype)),
         _p(_arr(absb, dtype)), C.c_double(freq), C.c_double(p0), C.c_double(s0), C.c_double(t0),
-        C.c_double(tf), C.c_double(dt), _p(u), _p(v)
+        C.c_double(tf), C.c_double(dt), _p(u), _p(v), _steps(steps)
     )
 
 
 def lossy_rk4(tdim, N, tensor_dofmap, G, D, lin_coeff, att_coeff, m, src, absb, src2, freq, p0, s0, t0, tf, dt,
-              u, v, dtype=np.float64, fast=False, source_scale=2.0):
+              u, v, dtype=np.float64, fast=False, source_scale=2.0, steps=None):
     """Lossy.hpp rk4 restated; u, v updated in place; returns the number of steps taken.
-    source_scale 2: Lossy.hpp:216-220; 1: the Python package's unscaled source (_lossy.py:186-189)."""
+    source_scale 2: Lossy.hpp:216-220; 1: the Python package's unscaled source (_lossy.py:186-189).
+    ``steps``: as linear_rk4."""
     dm = _arr(tensor_dofmap, np.int32)
-    fn = getattr(lib(fast), "orc_lossy_rk4_s_" + _suf(dtype))
+    fn = getattr(lib(fast), "orc_lossy_rk4_n_" + _suf(dtype))
     fn.restype = C.c_int64
     assert u.flags.c_contiguous and v.flags.c_contiguous
     return fn(
         C.c_int(tdim), C.c_int64(dm.shape[0]), C.c_int64(len(u)), C.c_int(N), _p(dm), _p(_arr(G, dtype)),
         _p(_arr(D, dtype)), _p(_arr(lin_coeff, dtype)), _p(_arr(att_coeff, dtype)), _p(_arr(m, dtype)),
         _p(_arr(src, dtype)), _p(_arr(absb, dtype)), _p(_arr(src2, dtype)), C.c_double(freq), C.c_double(p0),
-        C.c_double(s0), C.c_double(t0), C.c_double(tf), C.c_double(dt), _p(u), _p(v), C.c_double(source_scale)
+        C.c_double(s0), C.c_double(t0), C.c_double(tf), C.c_double(dt), _p(u), _p(v), C.c_double(source_scale),
+        _steps(steps)
     )
 
 
 def westervelt_rk4(tdim, N, tensor_dofmap, G, detJ, D, lin_coeff, att_coeff, nlin1, nlin2, m0, src, absb, src2,
-                   freq, p0, s0, t0, tf, dt, u, v, dtype=np.float64, fast=False, source_scale=2.0):
-    """Westervelt.hpp rk4 restated; u, v updated in place; returns the number of steps taken."""
+                   freq, p0, s0, t0, tf, dt, u, v, dtype=np.float64, fast=False, source_scale=2.0, steps=None):
+    """Westervelt.hpp rk4 restated; u, v updated in place; returns the number of steps taken.
+    ``steps``: as linear_rk4."""
     dm = _arr(tensor_dofmap, np.int32)
-    fn = getattr(lib(fast), "orc_westervelt_rk4_s_" + _suf(dtype))
+    fn = getattr(lib(fast), "orc_westervelt_rk4_n_" + _suf(dtype))
     fn.restype = C.c_int64
     assert u.flags.c_contiguous and v.flags.c_contiguous
     a = lambda x: _p(_arr(x, dtype))  # noqa: E731
@@ -210,7 +219,7 @@ def westervelt_rk4(tdim, N, tensor_dofmap, G, detJ, D, lin_coeff, att_coeff, nli
         C.c_int(tdim), C.c_int64(dm.shape[0]), C.c_int64(len(u)), C.c_int(N), _p(dm), a(G), a(detJ), a(D),
         a(lin_coeff), a(att_coeff), a(nlin1), a(nlin2), a(m0), a(src), a(absb), a(src2), C.c_double(freq),
         C.c_double(p0), C.c_double(s0), C.c_double(t0), C.c_double(tf), C.c_double(dt), _p(u), _p(v),
-        C.c_double(source_scale)
+        C.c_double(source_scale), _steps(steps)
     )
 
 

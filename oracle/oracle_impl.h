@@ -657,11 +657,16 @@ static void FN(k_axpy)(int64_t n, REAL* r, REAL alpha, const REAL* x, const REAL
  * The FFCx facet assembly (:205) is the diagonal form  b += g(t) src - absb .* v_n. */
 /* order: 4 = classical RK4 (Linear.hpp:263-265); 1, 2, 3 = forward Euler / Ralston tables of the
  * Python reference's rk() (python/src/fenicsxfus/_linear.py:286-311, loop :461-499). */
-int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, int N,
-                          const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
-                          const REAL* coeff, const REAL* m, const REAL* src, const REAL* absb,
-                          double freq_, double p0_, double s0_, double t0, double tf_, double dt_,
-                          REAL* u_n, REAL* v_n)
+/* nsteps < 0: the reference's loop, `while (t < tf)` with t in REAL and a shortened last step.
+ * nsteps >= 0: exactly nsteps full steps of dt (tf ignored); the loop time is kept in double and advanced by
+ * dt like the library's step loop, and handed to the stages rounded to REAL.  (In float the reference's own
+ * loop miscounts its steps: t accumulates a rounding per step and tf - t is a difference of floats.)  For
+ * REAL = double both loops do the same arithmetic wherever the first takes nsteps full steps. */
+int64_t FN(orc_linear_rk_n)(int order, int tdim, int64_t ncells, int64_t ndofs, int N,
+                            const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
+                            const REAL* coeff, const REAL* m, const REAL* src, const REAL* absb,
+                            double freq_, double p0_, double s0_, double t0, double tf_, double dt_,
+                            REAL* u_n, REAL* v_n, int64_t nsteps)
 {
   const REAL freq = (REAL)freq_, p0 = (REAL)p0_, s0 = (REAL)s0_;
   const REAL w0 = (REAL)(2 * M_PI * freq_);
@@ -672,6 +677,7 @@ int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, in
        *ku = (REAL*)malloc(nb), *kv = (REAL*)malloc(nb), *b = (REAL*)malloc(nb),
        *g = (REAL*)malloc(nb), *uw = (REAL*)malloc(nb), *vw = (REAL*)malloc(nb);
   REAL t = (REAL)t0, tf = (REAL)tf_, dt = (REAL)dt_;
+  double td = t0;
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
@@ -691,9 +697,10 @@ int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, in
     b_runge[0] = (REAL)(2.0 / 9.0), b_runge[1] = (REAL)(1.0 / 3.0), b_runge[2] = (REAL)(4.0 / 9.0);
     c_runge[1] = (REAL)(1.0 / 2.0), c_runge[2] = (REAL)(3.0 / 4.0);
   }
-  while (t < tf)
+  while (nsteps >= 0 ? step < nsteps : t < tf)
   {
-    dt = (dt < tf - t) ? dt : tf - t;
+    if (nsteps < 0)
+      dt = (dt < tf - t) ? dt : tf - t;
     FN(k_copy)(ndofs, u_, u0), FN(k_copy)(ndofs, v_, v0);
     for (int i = 0; i < order; i++)
     {
@@ -729,7 +736,8 @@ int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, in
       FN(k_axpy)(ndofs, u_, dt * b_runge[i], ku, u_);
       FN(k_axpy)(ndofs, v_, dt * b_runge[i], kv, v_);
     }
-    t += dt;
+    td += dt_;
+    t = nsteps >= 0 ? (REAL)td : t + dt;
     step += 1;
   }
   FN(k_copy)(ndofs, u_, u_n), FN(k_copy)(ndofs, v_, v_n);
@@ -738,6 +746,15 @@ int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, in
   return step;
 }
 
+int64_t FN(orc_linear_rk)(int order, int tdim, int64_t ncells, int64_t ndofs, int N,
+                          const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
+                          const REAL* coeff, const REAL* m, const REAL* src, const REAL* absb,
+                          double freq_, double p0_, double s0_, double t0, double tf_, double dt_,
+                          REAL* u_n, REAL* v_n)
+{
+  return FN(orc_linear_rk_n)(order, tdim, ncells, ndofs, N, tensor_dofmap, G, dphi, coeff, m, src, absb,
+                             freq_, p0_, s0_, t0, tf_, dt_, u_n, v_n, -1);
+}
 
 int64_t FN(orc_linear_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
                            const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
@@ -760,12 +777,13 @@ int64_t FN(orc_linear_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
 /* source_scale: 2 = the live "heterogenous domain" branch of Lossy.hpp:216-220; 1 = the Python
  * package (python/src/fenicsxfus/_lossy.py:186-189), which also keeps the absorbing and delta-mass
  * terms on tag 2 only -- that choice is in the vectors the caller passes (absb, m). */
-int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
+/* nsteps: as orc_linear_rk_n */
+int64_t FN(orc_lossy_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
                             const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
                             const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
                             const REAL* src, const REAL* absb, const REAL* src2, double freq_,
                             double p0_, double s0_, double t0, double tf_, double dt_, REAL* u_n,
-                            REAL* v_n, double source_scale)
+                            REAL* v_n, double source_scale, int64_t nsteps)
 {
   const REAL two = (REAL)source_scale;
   const REAL freq = (REAL)freq_, p0 = (REAL)p0_, s0 = (REAL)s0_;
@@ -777,6 +795,7 @@ int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
        *ku = (REAL*)malloc(nb), *kv = (REAL*)malloc(nb), *b = (REAL*)malloc(nb),
        *uw = (REAL*)malloc(nb), *vw = (REAL*)malloc(nb);
   REAL t = (REAL)t0, tf = (REAL)tf_, dt = (REAL)dt_;
+  double td = t0;
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
@@ -784,9 +803,10 @@ int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
   const REAL b_runge[4] = {(REAL)(1.0 / 6.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 3.0),
                            (REAL)(1.0 / 6.0)};
   const REAL c_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  while (t < tf)
+  while (nsteps >= 0 ? step < nsteps : t < tf)
   {
-    dt = (dt < tf - t) ? dt : tf - t;
+    if (nsteps < 0)
+      dt = (dt < tf - t) ? dt : tf - t;
     FN(k_copy)(ndofs, u_, u0), FN(k_copy)(ndofs, v_, v0);
     for (int i = 0; i < 4; i++)
     {
@@ -830,7 +850,8 @@ int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
       FN(k_axpy)(ndofs, u_, dt * b_runge[i], ku, u_);
       FN(k_axpy)(ndofs, v_, dt * b_runge[i], kv, v_);
     }
-    t += dt;
+    td += dt_;
+    t = nsteps >= 0 ? (REAL)td : t + dt;
     step += 1;
   }
   FN(k_copy)(ndofs, u_, u_n), FN(k_copy)(ndofs, v_, v_n);
@@ -839,6 +860,16 @@ int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
   return step;
 }
 
+int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
+                            const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
+                            const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
+                            const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                            double p0_, double s0_, double t0, double tf_, double dt_, REAL* u_n,
+                            REAL* v_n, double source_scale)
+{
+  return FN(orc_lossy_rk4_n)(tdim, ncells, ndofs, N, tensor_dofmap, G, dphi, lin_coeff, att_coeff, m,
+                             src, absb, src2, freq_, p0_, s0_, t0, tf_, dt_, u_n, v_n, source_scale, -1);
+}
 
 int64_t FN(orc_lossy_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
                           const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
@@ -857,13 +888,14 @@ int64_t FN(orc_lossy_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
  * M(nlin2) (v_n .* v_n)  (:246-247, :263, nlin2 = +2 beta/(rho^2 c^4), :186).  detJ is the scaled
  * Jacobian determinant the mass operator uses (spectral_op.hpp:80-81).  Other arguments as
  * orc_lossy_rk4 (m0 = its m). */
-int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
+/* nsteps: as orc_linear_rk_n */
+int64_t FN(orc_westervelt_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
                                  const int32_t* tensor_dofmap, const REAL* G, const REAL* detJ,
                                  const REAL* dphi, const REAL* lin_coeff, const REAL* att_coeff,
                                  const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,
                                  const REAL* src, const REAL* absb, const REAL* src2, double freq_,
                                  double p0_, double s0_, double t0, double tf_, double dt_,
-                                 REAL* u_n, REAL* v_n, double source_scale)
+                                 REAL* u_n, REAL* v_n, double source_scale, int64_t nsteps)
 {
   const REAL two = (REAL)source_scale;
   const REAL freq = (REAL)freq_, p0 = (REAL)p0_, s0 = (REAL)s0_;
@@ -876,6 +908,7 @@ int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
        *uw = (REAL*)malloc(nb), *vw = (REAL*)malloc(nb), *ww = (REAL*)malloc(nb),
        *m = (REAL*)malloc(nb);
   REAL t = (REAL)t0, tf = (REAL)tf_, dt = (REAL)dt_;
+  double td = t0;
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
@@ -883,9 +916,10 @@ int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
   const REAL b_runge[4] = {(REAL)(1.0 / 6.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 3.0),
                            (REAL)(1.0 / 6.0)};
   const REAL c_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  while (t < tf)
+  while (nsteps >= 0 ? step < nsteps : t < tf)
   {
-    dt = (dt < tf - t) ? dt : tf - t;
+    if (nsteps < 0)
+      dt = (dt < tf - t) ? dt : tf - t;
     FN(k_copy)(ndofs, u_, u0), FN(k_copy)(ndofs, v_, v0);
     for (int i = 0; i < 4; i++)
     {
@@ -939,13 +973,27 @@ int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
       FN(k_axpy)(ndofs, u_, dt * b_runge[i], ku, u_);
       FN(k_axpy)(ndofs, v_, dt * b_runge[i], kv, v_);
     }
-    t += dt;
+    td += dt_;
+    t = nsteps >= 0 ? (REAL)td : t + dt;
     step += 1;
   }
   FN(k_copy)(ndofs, u_, u_n), FN(k_copy)(ndofs, v_, v_n);
   free(u_), free(v_), free(un), free(vn), free(u0), free(v0), free(ku), free(kv), free(b), free(uw),
       free(vw), free(ww), free(m);
   return step;
+}
+
+int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
+                                 const int32_t* tensor_dofmap, const REAL* G, const REAL* detJ,
+                                 const REAL* dphi, const REAL* lin_coeff, const REAL* att_coeff,
+                                 const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,
+                                 const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                                 double p0_, double s0_, double t0, double tf_, double dt_,
+                                 REAL* u_n, REAL* v_n, double source_scale)
+{
+  return FN(orc_westervelt_rk4_n)(tdim, ncells, ndofs, N, tensor_dofmap, G, detJ, dphi, lin_coeff,
+                                  att_coeff, nlin1_coeff, nlin2_coeff, m0, src, absb, src2, freq_, p0_,
+                                  s0_, t0, tf_, dt_, u_n, v_n, source_scale, -1);
 }
 
 int64_t FN(orc_westervelt_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,

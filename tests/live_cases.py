@@ -6,6 +6,7 @@ import numpy as np
 
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import tag_box_boundary
+from fp32_budget import promoted
 from util import Problem, layer_and_face_regions, live_state
 
 F0, S0 = 0.5e6, 1500.0
@@ -20,6 +21,9 @@ class Case:
         t = len(n)
         self.kind, self.P, self.nsteps, self.order, self.dtype, self.seed = kind, P, nsteps, order, np.dtype(dtype), seed
         self.hi = [L * k / n[0] for k in n]                 # cubic cells
+        # BoxMesh moves interior vertices only: without one, a "perturbed" box is still a box of affine cells
+        assert not perturb or all(k >= 2 for k in n), f"perturb > 0 on {n}: no interior vertex, the cells stay affine"
+        self.n, self.perturb, self.mesh_order, self.warp = tuple(n), perturb, mesh_order, warp
         kw = dict(hi=self.hi, perturb=perturb, order=mesh_order, warp=warp)
         self.pr = Problem(orc, n, P, **kw)                   # fp64: the reference
         self.prt = self.pr if self.dtype == np.float64 else Problem(orc, n, P, dtype=dtype, **kw)
@@ -44,6 +48,14 @@ class Case:
         cid = self.pr.mesh._cidx
         self.far_corner = np.all([cid[a] >= n[a] - 2 for a in range(t)], axis=0)
         assert 0 < self.far_corner.sum() <= 8 and nc > 0
+        self._pr64r, self._refs = None, {}
+
+    @property
+    def pr64r(self):
+        """An fp32 case's problem in double on the float-rounded coordinates: what its double reference runs on."""
+        if self._pr64r is None:
+            self._pr64r = self.pr if self.dtype == np.float64 else promoted(self.orc, self.prt)
+        return self._pr64r
 
     def start(self, seed=None):
         return live_state(self.pr, self.seed if seed is None else seed, self.p0)
@@ -51,12 +63,13 @@ class Case:
     # ---- oracle ----------------------------------------------------------------------------------------------------
     def materials(self, scale_far_corner=None):
         """c0, rho0, delta0, beta0 per cell; ``scale_far_corner`` multiplies the family's own coefficient (c0 for
-        Linear, delta for Lossy, beta for Westervelt) of the far-corner cells (the negative controls)."""
+        Linear, delta for Lossy, beta for Westervelt) of the far-corner cells (the negative controls).  The values
+        are those the library is given: rounded to the case's dtype (and returned in double)."""
         c, rho, delta, beta = (a.copy() for a in (self.c, self.rho, self.delta, self.beta))
         if scale_far_corner is not None:
             a = {"linear": c, "lossy": delta, "westervelt": beta}[self.kind]
             a[self.far_corner] *= scale_far_corner
-        return c, rho, delta, beta
+        return tuple(a.astype(self.dtype).astype(np.float64) for a in (c, rho, delta, beta))
 
     def vectors(self, pr, change=None, eps=1e-6, scale_far_corner=None):
         """The oracle's model vectors on ``pr``; ``change`` scales one of them by 1 + eps:
@@ -81,42 +94,70 @@ class Case:
         return V
 
     def oracle(self, u0, v0, dtype=np.float64, change=None, eps=1e-6, t0=0.0, nsteps=None, order=None,
-               scale_far_corner=None, exact=False):
+               scale_far_corner=None, exact=False, fixed=False, pr=None, margin=None):
         """u, v after ``nsteps`` steps from (u0, v0) at t0: to tf = t0 + nsteps dt (1 - 1e-9) like model.rk(), or with
         ``exact`` to t0 + nsteps dt (1 + 1e-12), nsteps full steps like model.rk4_steps() (+ a ~1e-12 dt remainder
-        step, far below the tolerance)."""
-        pr = self.pr if np.dtype(dtype) == np.float64 else self.prt
+        step, far below the tolerance), or with ``fixed`` exactly nsteps full steps (the oracle's ``steps=``: the only
+        form whose float instantiation counts its steps right).  ``margin`` overrides the relative margin of tf.
+        ``pr``: the problem to run on (default: the fp64 mesh for double, the case's own for float)."""
+        if pr is None:
+            pr = self.pr if np.dtype(dtype) == np.float64 else self.prt
+        assert pr.dtype == np.dtype(dtype)
         V = self.vectors(pr, change, eps, scale_far_corner)
         u, v = np.array(u0, dtype=dtype), np.array(v0, dtype=dtype)
         ns = self.nsteps if nsteps is None else nsteps
-        tf = t0 + ns * self.dt * ((1 + 1e-12) if exact else (1 - 1e-9))
+        tf = t0 + ns * self.dt * (1 + (margin if margin is not None else (1e-12 if exact else -1e-9)))
         a = (self.tdim, pr.N, pr.dm, pr.G)
+        kw = dict(dtype=dtype, steps=ns if fixed else None)
         if self.kind == "linear":
             k = self.orc.linear_rk4(*a, pr.D, V["coeff"], V["m"], V["src"], V["absb"], F0, self.p0, S0, t0, tf,
-                                    self.dt, u, v, dtype=dtype, order=self.order if order is None else order)
+                                    self.dt, u, v, order=self.order if order is None else order, **kw)
         elif self.kind == "lossy":
             k = self.orc.lossy_rk4(*a, pr.D, V["coeff"], V["att"], V["m"], V["src"], V["absb"], V["src2"], F0, self.p0,
-                                   S0, t0, tf, self.dt, u, v, dtype=dtype)
+                                   S0, t0, tf, self.dt, u, v, **kw)
         else:
             k = self.orc.westervelt_rk4(*a, pr.detJ, pr.D, V["coeff"], V["att"], V["n1"], -V["n1"], V["m"], V["src"],
-                                        V["absb"], V["src2"], F0, self.p0, S0, t0, tf, self.dt, u, v, dtype=dtype)
-        assert k == ns or (exact and k == ns + 1)
+                                        V["absb"], V["src2"], F0, self.p0, S0, t0, tf, self.dt, u, v, **kw)
+        assert k == ns or (exact and not fixed and k == ns + 1)
         return u, v
 
+    def fp32_refs(self, nsteps=None, change=None, eps=1e-4, scale_far_corner=None):
+        """An fp32 case's (start in float, r32, r64) after exactly ``nsteps`` steps (fp32_budget.py): r32 the float
+        oracle on the case's float inputs, r64 the double oracle on the same inputs promoted to double."""
+        assert self.dtype == np.float32
+        key = (nsteps, change, eps, scale_far_corner)
+        if key not in self._refs:
+            u0, v0 = (a.astype(np.float32) for a in self.start())
+            kw = dict(change=change, eps=eps, nsteps=nsteps, scale_far_corner=scale_far_corner, fixed=True)
+            r32 = self.oracle(u0, v0, dtype=np.float32, **kw)
+            r64 = self.oracle(u0, v0, pr=self.pr64r, **kw)
+            self._refs[key] = ((u0, v0), r32, r64)
+        return self._refs[key]
+
     # ---- GPU model ---------------------------------------------------------------------------------------------------
-    def model(self, ctx, scale_far_corner=None, order=None):
-        """The library's model of this case (``scale_far_corner``: see materials())."""
-        pr, dt_ = self.prt, self.dtype
-        c, rho, delta, beta = (np.array(a, dtype=dt_) for a in self.materials(scale_far_corner))
+    def model(self, ctx, scale_far_corner=None, order=None, rank=None, size=1):
+        """The library's model of this case (``scale_far_corner``: see materials()); ``rank`` of ``size``: of that
+        x-slab of the case's mesh (first-order meshes; the slab's cells are a contiguous range of the global ones)."""
+        dt_ = self.dtype
+        mats = self.materials(scale_far_corner)
+        if rank is None:
+            mesh, V = self.prt.mesh, self.prt.V
+        else:
+            assert self.mesh_order == 1
+            mesh = fa.BoxMesh([0.0] * self.tdim, self.hi, self.n, rank=rank, size=size, perturb=self.perturb, dtype=dt_)
+            V = fa.FunctionSpace(mesh, self.P)
+            per_layer = self.pr.mesh.num_cells // self.n[0]
+            mats = tuple(a[mesh.cx0 * per_layer:mesh.cx1 * per_layer] for a in mats)
+        c, rho, delta, beta = (np.array(a, dtype=dt_) for a in mats)
         o = self.order if order is None else order
-        tags = tag_box_boundary(pr.mesh)
+        tags = tag_box_boundary(mesh)
         if self.kind == "linear":
-            return fa.LinearSpectralExplicit(pr.mesh, tags, self.P, c, rho, F0, self.p0, S0, o, self.dt, V=pr.V, ctx=ctx)
+            return fa.LinearSpectralExplicit(mesh, tags, self.P, c, rho, F0, self.p0, S0, o, self.dt, V=V, ctx=ctx)
         if self.kind == "lossy":
-            return fa.LossySpectralExplicit(pr.mesh, tags, self.P, c, rho, delta, F0, self.p0, S0, o, self.dt, V=pr.V,
+            return fa.LossySpectralExplicit(mesh, tags, self.P, c, rho, delta, F0, self.p0, S0, o, self.dt, V=V,
                                             ctx=ctx)
-        return fa.WesterveltSpectralExplicit(pr.mesh, tags, self.P, c, rho, delta, beta, F0, self.p0, S0, o, self.dt,
-                                             V=pr.V, ctx=ctx)
+        return fa.WesterveltSpectralExplicit(mesh, tags, self.P, c, rho, delta, beta, F0, self.p0, S0, o, self.dt,
+                                             V=V, ctx=ctx)
 
 
 # name -> (constructor keywords).  Non-cubic meshes so that blocks are ragged.
@@ -130,9 +171,9 @@ for _o in (1, 2, 3):
 CASES["linear-walk"] = dict(kind="linear", n=(16, 12, 12), P=4, nsteps=10, L=0.016)
 for _P in (2, 3, 5, 6, 7):
     CASES[f"linear-p{_P}"] = dict(kind="linear", n=(4, 3, 2) if _P <= 5 else (3, 2, 2), P=_P)
-for _P in (8, 10):
+for _P in (8, 9, 10):      # (2, 2, 2): one interior vertex, all eight cells distorted
     for _kind in ("linear", "westervelt"):
-        CASES[f"{_kind}-p{_P}"] = dict(kind=_kind, n=(2, 2, 1), P=_P, nsteps=6)
+        CASES[f"{_kind}-p{_P}"] = dict(kind=_kind, n=(2, 2, 2), P=_P, nsteps=6)
 for _P, _n in ((4, (5, 4, 3)), (6, (4, 3, 2))):
     CASES[f"linear-p{_P}-fp32"] = dict(kind="linear", n=_n, P=_P, dtype=np.float32)
 for _P, _n in ((4, (9, 7)), (9, (4, 3))):
@@ -142,6 +183,35 @@ CASES["linear-q2"] = dict(kind="linear", n=(4, 3, 3), P=4, perturb=0.0, mesh_ord
                           warp=lambda x: x + np.c_[20.0 * x[:, 1] ** 2 - 12.0 * x[:, 2] ** 2, 15.0 * x[:, 2] ** 2,
                                                    0 * x[:, 0]])
 
+# ---- the fp32 cases held to the float oracle's own rounding error (fp32_budget.py) -----------------------------------
+KINDS = ("linear", "lossy", "westervelt")
+
+
+def _hex_n(P):
+    return (6, 5, 4) if P <= 4 else ((3, 3, 2) if P <= 7 else (2, 2, 2))
+
+
+FP32_RUNS = {}       # every family, every degree: perturbed (trilinear / stream) and box (diagonal metric / affine)
+for _kind in KINDS:
+    for _P in range(2, 11):
+        _kw = dict(kind=_kind, n=_hex_n(_P), P=_P, nsteps=10 if _P < 8 else 6, dtype=np.float32)
+        FP32_RUNS[f"{_kind}-p{_P}"] = dict(_kw)
+        FP32_RUNS[f"{_kind}-p{_P}-box"] = dict(_kw, perturb=0.0)
+    FP32_RUNS[f"{_kind}-quad-p4"] = dict(kind=_kind, n=(9, 7), P=4, dtype=np.float32)
+    FP32_RUNS[f"{_kind}-quad-p9"] = dict(kind=_kind, n=(4, 3), P=9, nsteps=6, dtype=np.float32)
+FP32_RUNS["linear-q2"] = dict(CASES["linear-q2"], dtype=np.float32)
+# configs[4]'s arithmetic over a longer run: rounding accumulates like a random walk.  50 steps, not 200: the float
+# oracle's own error in v (largest measure, in ulp of 2^-23) is 60 / 90 / 278 / 508 after 25 / 50 / 100 / 200 steps, and
+# a yardstick above 128 ulp would make the comparison vacuous (test_fp32_guards.py); 50 is the longest power-of-two
+# multiple of 25 steps that keeps it.
+FP32_LONG = {"linear-p6-long": dict(kind="linear", n=(4, 3, 2), P=6, nsteps=50, dtype=np.float32)}
+# two x-slabs (test_gpu_config5_fp32.py's partition in small)
+FP32_SLABS = {f"{_kind}-slabs-p{_P}": dict(kind=_kind, n=_n, P=_P, L=0.024, nsteps=15, dtype=np.float32)
+              for _kind in ("lossy", "westervelt") for _P, _n in ((6, (6, 3, 3)), (4, (8, 4, 4)))}
+# enough blocks (320 of two elements) for walking workgroups to walk: more blocks than the device has CUs
+FP32_WALK = {f"{_kind}-walk-p{_P}": dict(kind=_kind, n=(10, 8, 8), P=_P, L=0.02, dtype=np.float32)
+             for _kind in ("linear", "westervelt") for _P in (4, 6)}
+FP32_CASES = {**FP32_RUNS, **FP32_LONG, **FP32_SLABS, **FP32_WALK}
 
 _cache = {}
 
@@ -150,3 +220,9 @@ def case(orc, name) -> Case:
     if name not in _cache:
         _cache[name] = Case(orc, **CASES[name])
     return _cache[name]
+
+
+def fp32_case(orc, name) -> Case:
+    if ("fp32", name) not in _cache:
+        _cache["fp32", name] = Case(orc, **FP32_CASES[name])
+    return _cache["fp32", name]

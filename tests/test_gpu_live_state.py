@@ -123,11 +123,15 @@ def test_graph_replay(orc):
     cx.close()
 
 
-@pytest.mark.parametrize("name", ["linear-p2", "linear-p3", "linear-p5", "linear-p8", "westervelt-p8", "linear-p10",
-                                  "westervelt-p10"])
+@pytest.mark.parametrize("name", ["linear-p2", "linear-p3", "linear-p5", "linear-p8", "westervelt-p8", "linear-p9",
+                                  "westervelt-p9", "linear-p10", "westervelt-p10"])
 def test_degrees(orc, name):
+    """Perturbed first-order hexahedra: the trilinear kernels (degrees 8-10: elem_compute_hi on distorted cells)."""
     cs, u0, v0, ref = live_reference(orc, name)
     cx = fa.Context(0)
+    model = cs.model(cx)
+    assert cs.perturb > 0 and model.data.geometry_mode() == "trilinear"
+    model.close()
     check(run_gpu(cs, cx, u0, v0), ref, TOL_RK)
     cx.close()
 

@@ -4,7 +4,9 @@ of its max) in every element layer, on every boundary face and on every interfac
 within 10x the start's max over the run; and a 1e-6 relative change of the far face's absorbing weight, of the last
 layer's stiffness coefficient and (multi-rank) of the mass on either side of each cut moves the oracle state by at
 least 100x the fp64 RK tolerance -- so the GPU comparison at that tolerance would see such a mistake.  (The fp32
-cases are guarded through their fp64 reference: the GPU comparison in fp32 is the weaker one by construction.)"""
+cases here are guarded through their fp64 reference: their GPU comparison at a fixed fp32 tolerance is the weaker one
+by construction.  The fp32 comparisons that see a 1e-4 mistake are those of test_gpu_fp32_budget.py, guarded by
+test_fp32_guards.py.)"""
 import numpy as np
 import pytest
 
