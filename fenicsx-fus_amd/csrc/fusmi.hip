@@ -282,6 +282,14 @@ struct fus_model
   int rec_every = 0, rec_which = 0;
   int64_t rec_cap = 0, rec_n = 0, rec_step = 0;
   std::vector<double> rec_times;
+  // field monitor (fus_model_monitor): per-DOF accumulator planes over the internal vector, one allocation --
+  // T[2][n_internal] (max, min) then double[2 + 2 nharm][n_internal] (sum, sum of squares, cos_k, sin_k)
+  void* d_mon = nullptr;
+  size_t mon_bytes = 0;
+  int mon_every = 0, mon_which = 0, mon_nharm = 0;
+  double mon_freq = 0.0;
+  int64_t mon_skip = 0, mon_count = 0, mon_step = 0, mon_n = 0;
+  double mon_t_first = 0.0, mon_t_last = 0.0;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -1918,6 +1926,73 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
 // -------------------------------------------------------------------------------------------------
 // C ABI
 // -------------------------------------------------------------------------------------------------
+// ---- field monitor: typed launches (the C entry points are fus_model_monitor* below) ----
+template <typename T, int NH>
+static void launch_monitor(fus_model* m, const double* c, const double* s)
+{
+  const int64_t n = m->op->L.n_internal;
+  const int64_t nvec = n / (16 / (int64_t)sizeof(T));
+  MonPhase<NH> ph{};
+  for (int k = 0; k < NH; ++k)
+    ph.c[k] = c[k], ph.s[k] = s[k];
+  const unsigned grid = (unsigned)std::min<int64_t>((nvec + 255) / 256, (int64_t)m->ctx->num_cus * 8);
+  T* ext = static_cast<T*>(m->d_mon);
+  double* acc = reinterpret_cast<double*>(ext + 2 * n);
+  hipLaunchKernelGGL((k_monitor_accumulate<T, NH>), dim3(grid), dim3(256), 0, m->ctx->stream, nvec, n,
+                     m->mon_n == 0 ? 1 : 0, static_cast<const T*>(m->mon_which == FUS_U ? m->u0 : m->v0), ext, acc, ph);
+}
+
+template <typename T>
+static void launch_monitor_nh(fus_model* m, const double* c, const double* s)
+{
+  switch (m->mon_nharm)
+  {
+  case 0: launch_monitor<T, 0>(m, c, s); break;
+  case 1: launch_monitor<T, 1>(m, c, s); break;
+  case 2: launch_monitor<T, 2>(m, c, s); break;
+  case 3: launch_monitor<T, 3>(m, c, s); break;
+  case 4: launch_monitor<T, 4>(m, c, s); break;
+  case 5: launch_monitor<T, 5>(m, c, s); break;
+  case 6: launch_monitor<T, 6>(m, c, s); break;
+  case 7: launch_monitor<T, 7>(m, c, s); break;
+  default: launch_monitor<T, 8>(m, c, s); break;
+  }
+}
+
+template <typename T>
+static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t n = op->L.n_internal;
+  const T* ext = static_cast<const T*>(m->d_mon);
+  const double* acc = reinterpret_cast<const double*>(ext + 2 * n);
+  const T* src = nullptr;
+  if (quantity == FUS_MON_MAX || quantity == FUS_MON_MIN)
+    src = ext + (quantity == FUS_MON_MIN ? n : 0);   // already a T vector in internal numbering
+  else
+  {
+    const int plane = quantity == FUS_MON_MEAN ? 0 : quantity == FUS_MON_RMS ? 1
+                      : quantity == FUS_MON_COS ? 1 + k : 1 + m->mon_nharm + k;
+    const double num = (quantity == FUS_MON_COS || quantity == FUS_MON_SIN) ? 2.0 : 1.0;
+    T* fin = static_cast<T*>(op->d_tmp_x);
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)m->ctx->num_cus * 8);
+    hipLaunchKernelGGL((k_monitor_finalise<T>), dim3(grid), dim3(256), 0, st, n, acc + (size_t)plane * n, num,
+                       (double)m->mon_n, quantity == FUS_MON_RMS ? 1 : 0, fin);
+    src = fin;
+  }
+  T* tc = static_cast<T*>(op->d_tmp_c);
+  T* dst = space == FUS_HOST ? tc : static_cast<T*>(out);
+  hipLaunchKernelGGL((k_from_internal<T, 0>), dim3(nblk(op->ndofs)), dim3(256), 0, st, op->ndofs, op->d_dof_perm, src, dst);
+  if (space == FUS_HOST)
+    HIPCHK(hipMemcpyAsync(out, tc, op->ndofs * sizeof(T), hipMemcpyDeviceToHost, st));
+  if (src == op->d_tmp_x)   // the operator's scratch vector keeps zeros in its padding slots
+    HIPCHK(hipMemsetAsync(op->d_tmp_x, 0, (size_t)n * sizeof(T), st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
 extern "C"
 {
 
@@ -2589,6 +2664,8 @@ int fus_group_finish_setup(fus_model** ms, int n)
   return FUS_OK;
 }
 
+static int model_after_step(fus_model* m, double t);   // field monitor, defined with fus_model_monitor below
+
 int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nsteps)
 {
   if (!ms || n < 1)
@@ -2614,6 +2691,8 @@ int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nst
       for (int i = 0; i < n; ++i)
         std::swap(ms[i]->u_, ms[i]->u0), std::swap(ms[i]->v_, ms[i]->v0);
     t += dt;
+    for (int i = 0; i < n; ++i)
+      FUSCHK(model_after_step(ms[i], t));
   }
   for (int i = 0; i < n; ++i)
     HIPCHK(hipStreamSynchronize(ms[i]->ctx->stream));
@@ -2707,6 +2786,8 @@ int fus_model_stage_end(fus_model* m, int stage, double t, double dt)
   FUSCHK(d_stage_end(m, stage, t, dt));
   if (stage == m->rk_order - 1 && m->rk_order != 4)
     std::swap(m->u_, m->u0), std::swap(m->v_, m->v0);  // the accumulated solution is the new state
+  if (stage == m->rk_order - 1)
+    FUSCHK(model_after_step(m, t + dt));
   return FUS_OK;
 }
 
@@ -2731,6 +2812,8 @@ int fus_model_destroy(fus_model* m)
     m->op->bnd_owner = nullptr;
   for (void* q : m->allocs)
     (void)hipFree(q);
+  if (m->d_mon)
+    (void)hipFree(m->d_mon);
   delete m;
   return FUS_OK;
 }
@@ -2897,6 +2980,114 @@ int fus_model_get_records(fus_model* m, void* out, double* times, int64_t* nrec)
   return FUS_OK;
 }
 
+// ---- field monitor: whole-field maps over a window of steps, accumulated on the device (fusmi.h) ----
+static size_t monitor_bytes(const fus_model* m, int nharm)
+{
+  return (size_t)m->op->L.n_internal * (2 * m->op->ts + (size_t)(2 + 2 * nharm) * sizeof(double));
+}
+
+// after a step that ended at time t (s = steps since fus_model_monitor): a sample when s > skip,
+// (s - skip) % every == 0 and the count allows; an ordinary launch on the model's stream, nothing when off.
+// No hipSetDevice here: the callers have made the model's device current, and fus_group_rk4_steps launches it,
+// like the stage calls of its loop, with the device that is current -- the members of a group share one device.
+static int model_after_step(fus_model* m, double t)
+{
+  if (m->mon_every <= 0)
+    return FUS_OK;
+  const int64_t s = ++m->mon_step;
+  if (s <= m->mon_skip || (s - m->mon_skip) % m->mon_every != 0 || (m->mon_count > 0 && m->mon_n >= m->mon_count))
+    return FUS_OK;
+  double c[8], sn[8];
+  for (int k = 1; k <= m->mon_nharm; ++k)
+  {
+    const double arg = 2.0 * M_PI * k * m->mon_freq * t;
+    c[k - 1] = std::cos(arg), sn[k - 1] = std::sin(arg);
+  }
+  {
+    ProfScope ps(m->ctx, "monitor");
+    if (m->op->dtype == FUS_F64)
+      launch_monitor_nh<double>(m, c, sn);
+    else
+      launch_monitor_nh<float>(m, c, sn);
+  }
+  HIPCHK(hipGetLastError());
+  if (m->mon_n == 0)
+    m->mon_t_first = t;
+  m->mon_t_last = t;
+  ++m->mon_n;
+  return FUS_OK;
+}
+
+int fus_model_monitor(fus_model* m, int which, int nharm, double freq, int64_t skip, int every, int64_t count)
+{
+  if (!m)
+    return fail(FUS_ERR_ARG, "null model");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  if (every == 0)
+  {
+    HIPCHK(hipStreamSynchronize(m->ctx->stream));
+    if (m->d_mon)
+      (void)hipFree(m->d_mon);
+    m->d_mon = nullptr, m->mon_bytes = 0, m->mon_every = 0, m->mon_n = 0, m->mon_step = 0;
+    return FUS_OK;
+  }
+  if ((which != FUS_U && which != FUS_V) || nharm < 0 || nharm > 8 || every < 0 || skip < 0 || count < 0
+      || !(freq >= 0.0) || !std::isfinite(freq))
+    return fail(FUS_ERR_ARG, "fus_model_monitor: which is FUS_U | FUS_V, nharm 0..8, freq >= 0, skip >= 0, every > 0 (0: off), count >= 0");
+  const size_t bytes = monitor_bytes(m, nharm);
+  if (bytes != m->mon_bytes)
+  {
+    HIPCHK(hipStreamSynchronize(m->ctx->stream));
+    if (m->d_mon)
+      (void)hipFree(m->d_mon);
+    m->d_mon = nullptr, m->mon_bytes = 0, m->mon_every = 0;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return fail(FUS_ERR_HIP, "fus_model_monitor: cannot allocate " + std::to_string(bytes)
+                                   + " bytes of accumulators: " + hipGetErrorString(e));
+    }
+    m->d_mon = q, m->mon_bytes = bytes;
+  }
+  HIPCHK(hipMemsetAsync(m->d_mon, 0, bytes, m->ctx->stream));
+  m->mon_which = which, m->mon_nharm = nharm, m->mon_freq = freq == 0.0 ? m->freq : freq;
+  m->mon_skip = skip, m->mon_every = every, m->mon_count = count;
+  m->mon_step = 0, m->mon_n = 0, m->mon_t_first = m->mon_t_last = 0.0;
+  return FUS_OK;
+}
+
+int fus_model_monitor_info(fus_model* m, int64_t* nsamples, double* t_first, double* t_last)
+{
+  if (!m)
+    return fail(FUS_ERR_ARG, "null model");
+  if (m->mon_every <= 0)
+    return fail(FUS_ERR_STATE, "the monitor is off (fus_model_monitor)");
+  if (nsamples)
+    *nsamples = m->mon_n;
+  if (t_first)
+    *t_first = m->mon_t_first;
+  if (t_last)
+    *t_last = m->mon_t_last;
+  return FUS_OK;
+}
+
+int fus_model_monitor_get(fus_model* m, int quantity, int k, void* out, int space)
+{
+  if (!m || !out || quantity < FUS_MON_MAX || quantity > FUS_MON_SIN || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_model_monitor_get: bad model, quantity, out or space");
+  if (m->mon_every <= 0)
+    return fail(FUS_ERR_STATE, "the monitor is off (fus_model_monitor)");
+  if ((quantity == FUS_MON_COS || quantity == FUS_MON_SIN) && (k < 1 || k > m->mon_nharm))
+    return fail(FUS_ERR_ARG, "fus_model_monitor_get: harmonic k outside 1..nharm");
+  if (m->mon_n == 0)
+    return fail(FUS_ERR_STATE, "the monitor has taken no sample yet");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  return m->op->dtype == FUS_F64 ? monitor_get<double>(m, quantity, k, out, space)
+                                 : monitor_get<float>(m, quantity, k, out, space);
+}
+
 int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nsteps)
 {
   if (!m)
@@ -2919,6 +3110,7 @@ int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nste
       t += dt;
       ++step;
       FUSCHK(model_record_step(m, t));
+      FUSCHK(model_after_step(m, t));
     }
   }
   else
@@ -2931,6 +3123,7 @@ int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nste
       t += dt;
       ++step;
       FUSCHK(model_record_step(m, t));
+      FUSCHK(model_after_step(m, t));
     }
   }
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
@@ -2954,6 +3147,7 @@ int fus_model_rk4_steps(fus_model* m, double t0, double dt, int64_t nsteps)
     FUSCHK(d_model_step(m, t, dt));
     t += dt;
     FUSCHK(model_record_step(m, t));
+    FUSCHK(model_after_step(m, t));
   }
   return FUS_OK;
 }

@@ -3547,6 +3547,78 @@ __global__ void __launch_bounds__(256) k_stream_copy(int64_t nvec, const V* __re
     __builtin_nontemporal_store(__builtin_nontemporal_load(x + i), y + i);
 }
 
+// ---- steady-state field monitor (fus_model_monitor, fusmi.h) ---------------------------------------------------
+// One sample = one streaming read-modify-write pass over the per-DOF accumulator planes (structure of arrays, each
+// plane n = n_internal long, n a multiple of 16):
+//   ext  T[2][n]               running max, running min
+//   acc  double[2 + 2 NH][n]   sum, sum of squares, cos_1..cos_NH, sin_1..sin_NH  (always fp64, also for T = float)
+// A thread takes 16 bytes of the state (2 doubles / 4 floats) and updates every plane of those DOFs: one read of the
+// state, one read and one write of each plane, all 16-byte accesses, the planes non-temporal (they are streamed once
+// per sample and are far larger than the last-level cache at production sizes).  The 2 NH phase factors
+// cos / sin(2 pi k f t_j) are computed on the host in double and arrive by value in the kernarg segment; NH is a
+// template parameter so that the plane loop unrolls and nothing is indexed at run time (no scratch).
+// first != 0: the first sample of a window -- max = min = x without reading the (zeroed) extremum planes.
+template <int NH>
+struct MonPhase
+{
+  double c[NH > 0 ? NH : 1], s[NH > 0 ? NH : 1];
+};
+
+template <typename T, int NH>
+__global__ void __launch_bounds__(256)
+k_monitor_accumulate(int64_t nvec, int64_t n, int first, const T* __restrict__ x, T* __restrict__ ext,
+                     double* __restrict__ acc, const MonPhase<NH> ph)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV xv = *reinterpret_cast<const TV*>(x + i * VEC);
+    TV* pmax = reinterpret_cast<TV*>(ext + i * VEC);
+    TV* pmin = reinterpret_cast<TV*>(ext + n + i * VEC);
+    TV mx = xv, mn = xv;
+    if (!first)
+    {
+      const TV omx = __builtin_nontemporal_load(pmax), omn = __builtin_nontemporal_load(pmin);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        mx[j] = xv[j] > omx[j] ? xv[j] : omx[j], mn[j] = xv[j] < omn[j] ? xv[j] : omn[j];
+    }
+    __builtin_nontemporal_store(mx, pmax);
+    __builtin_nontemporal_store(mn, pmin);
+#pragma unroll
+    for (int h = 0; h < VEC / 2; ++h)
+    {
+      const D2 xd = {(double)xv[2 * h], (double)xv[2 * h + 1]};
+      D2* p = reinterpret_cast<D2*>(acc + i * VEC + 2 * h);
+      const int64_t stride = n / 2;   // plane stride in D2
+      __builtin_nontemporal_store(__builtin_nontemporal_load(p) + xd, p);
+      __builtin_nontemporal_store(__builtin_nontemporal_load(p + stride) + xd * xd, p + stride);
+#pragma unroll
+      for (int k = 0; k < NH; ++k)
+      {
+        D2* pc = p + (2 + k) * stride;
+        D2* ps = p + (2 + NH + k) * stride;
+        __builtin_nontemporal_store(__builtin_nontemporal_load(pc) + xd * ph.c[k], pc);
+        __builtin_nontemporal_store(__builtin_nontemporal_load(ps) + xd * ph.s[k], ps);
+      }
+    }
+  }
+}
+
+// Monitor read-out in internal numbering: out = (num * plane) / den, or its square root (RMS), rounded to T.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_monitor_finalise(int64_t n, const double* __restrict__ plane, double num, double den, int root, T* __restrict__ out)
+{
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+  {
+    const double q = (num * plane[i]) / den;
+    out[i] = (T)(root ? sqrt(q) : q);
+  }
+}
+
 // halo helpers
 // pack: sendbuf[k] = vec[idx[k]] over the concatenated neighbour lists
 // Receiver sampling (the reference evaluates its solution at points with Function::eval after locating their cells:

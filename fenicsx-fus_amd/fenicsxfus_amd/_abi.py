@@ -14,6 +14,7 @@ FUS_F32, FUS_F64 = 0, 1
 FUS_HOST, FUS_DEVICE = 0, 1
 FUS_LINEAR, FUS_LOSSY, FUS_WESTERVELT = 0, 1, 2
 FUS_U, FUS_V = 0, 1
+FUS_MON_MAX, FUS_MON_MIN, FUS_MON_MEAN, FUS_MON_RMS, FUS_MON_COS, FUS_MON_SIN = range(6)
 
 # every symbol include/fusmi.h declares
 SYMBOLS = [
@@ -27,6 +28,7 @@ SYMBOLS = [
     "fus_model_setup_count", "fus_model_setup_pack", "fus_model_setup_unpack", "fus_model_setup_finish",
     "fus_model_stage_begin", "fus_model_stage_end",
     "fus_model_set_receivers", "fus_model_sample", "fus_model_record", "fus_model_get_records",
+    "fus_model_monitor", "fus_model_monitor_get", "fus_model_monitor_info",
 ]
 
 

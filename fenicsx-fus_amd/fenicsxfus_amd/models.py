@@ -164,6 +164,42 @@ class _SpectralExplicit:
         check(lib().fus_model_get_records(self.h, ptr(out), ptr(times), C.byref(n)))
         return times, out
 
+    # ---- field monitor: whole-field maps accumulated on the device over a window of steps (fusmi.h) ----
+    _MON = {"max": _abi.FUS_MON_MAX, "min": _abi.FUS_MON_MIN, "mean": _abi.FUS_MON_MEAN, "rms": _abi.FUS_MON_RMS,
+            "cos": _abi.FUS_MON_COS, "sin": _abi.FUS_MON_SIN}
+
+    def monitor(self, which: str = "u", nharm: int = 0, freq: float | None = None, skip: int = 0, every: int = 1,
+                count: int = 0):
+        """After every ``every``-th step past the first ``skip`` steps (at most ``count`` times; 0 = no cap) fold
+        u (or v) into per-DOF running max / min, sum, sum of squares and the cosine / sine sums of the harmonics
+        1..``nharm`` of ``freq`` (default: the source frequency).  Restarts the window; ``every=0`` is monitor_off()."""
+        if which not in ("u", "v"):
+            raise _abi.FusError(f"unknown monitor field {which!r}: \"u\" or \"v\"")
+        w = _abi.FUS_U if which == "u" else _abi.FUS_V
+        check(lib().fus_model_monitor(self.h, C.c_int(w), C.c_int(nharm), C.c_double(0.0 if freq is None else freq),
+                                      C.c_int64(skip), C.c_int(every), C.c_int64(count)))
+
+    def monitor_off(self):
+        """Stop sampling and free the accumulators."""
+        check(lib().fus_model_monitor(self.h, C.c_int(_abi.FUS_U), C.c_int(0), C.c_double(0.0), C.c_int64(0), C.c_int(0),
+                                      C.c_int64(0)))
+
+    def monitor_info(self):
+        """(number of samples, time of the first sample, time of the last sample)."""
+        n, t0, t1 = C.c_int64(), C.c_double(), C.c_double()
+        check(lib().fus_model_monitor_info(self.h, C.byref(n), C.byref(t0), C.byref(t1)))
+        return n.value, t0.value, t1.value
+
+    def monitor_get(self, name: str, k: int | None = None) -> Function:
+        """The map ``name`` in "max", "min", "mean", "rms", "cos", "sin" (the last two: harmonic ``k`` >= 1) as a
+        Function on the model's space (what output.write_vtu takes)."""
+        if name not in self._MON:
+            raise _abi.FusError(f"unknown monitor quantity {name!r}: one of {sorted(self._MON)}")
+        f = Function(self.V, self.data.dtype)
+        check(lib().fus_model_monitor_get(self.h, C.c_int(self._MON[name]), C.c_int(0 if k is None else k),
+                                          ptr(f.x.array), C.c_int(_abi.FUS_HOST)))
+        return f
+
     def u_sol(self):
         self._pull()
         return self.u_n

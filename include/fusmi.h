@@ -276,6 +276,48 @@ int fus_model_sample(fus_model* model, int which, void* out, int space);
 int fus_model_record(fus_model* model, int which, int every, int64_t capacity);
 int fus_model_get_records(fus_model* model, void* out, double* times, int64_t* nrec);
 
+/* ---- field monitor: whole-field maps over the last source periods, accumulated on the device ---------
+ * What a focused-ultrasound user reads from a run -- peak positive / peak negative pressure, RMS pressure, amplitude
+ * and phase of the fundamental and its harmonics (the reference validates its Westervelt runs against the Fubini
+ * series, python/tests/test_westerveltspectral_1d.py:85-111) -- without a full-vector copy per step: after selected
+ * steps one kernel folds the resident state into per-DOF accumulators in HBM (the receivers' pattern, from points
+ * to the whole field).
+ *
+ * Sampling.  Let s be the number of steps completed since fus_model_monitor was called.  After step s a sample j is
+ * taken when   s > skip   and   (s - skip) % every == 0   and   (count == 0 or fewer than count samples so far).
+ * The sampled vector x_j is the one fus_model_get returns for `which` (FUS_U | FUS_V) at that moment; the sample
+ * time t_j is the step's end time as the time loop holds it (the value the receivers' records carry; in
+ * fus_model_rk4 with FUS_F32 the float time, in fus_model_stage_end t + dt).  Steps are counted in fus_model_rk4,
+ * fus_model_rk4_steps, fus_group_rk4_steps (every member) and in fus_model_stage_end of the last stage.
+ * Accumulators, per DOF of the internal vector (n_internal of them, fus_op_info out[7]):
+ *   running max  max_j x_j, running min  min_j x_j                                    type T
+ *   sum  S = sum_j x_j,  sum of squares  Q = sum_j x_j^2                              double
+ *   C_k = sum_j x_j cos(2 pi k f t_j),  S_k = sum_j x_j sin(2 pi k f t_j), k = 1..nharm    double
+ * The sums are double also for FUS_F32 models.  The 2 nharm phase factors of a sample are computed on the host in
+ * double and passed to the kernel by value; the kernel calls no trigonometric function.
+ * Returned quantities, n = number of samples:
+ *   FUS_MON_MAX  running max          FUS_MON_MIN  running min
+ *   FUS_MON_MEAN S / n                FUS_MON_RMS  sqrt(Q / n)
+ *   FUS_MON_COS  (2 / n) C_k          FUS_MON_SIN  (2 / n) S_k
+ * Over a window of whole periods with uniform sampling, x ~ MEAN + sum_k COS_k cos(2 pi k f t) + SIN_k sin(2 pi k f t).
+ * Aliasing: the samples per period, 1 / (f dt every), must exceed 2 nharm.
+ * Memory: n_internal * (2 sizeof(T) + (2 + 2 nharm) * 8) bytes of accumulators; a sample reads the state once and
+ * reads and writes every accumulator once.
+ *   fus_model_monitor       nharm in 0..8; freq == 0: the model's source frequency; every == 0 switches the monitor
+ *                           off and frees the accumulators; any other call allocates and zeroes them and restarts
+ *                           s and n (FUS_ERR_HIP naming the bytes asked for when the allocation fails; a failed
+ *                           restart leaves the monitor off, the earlier accumulators are gone)
+ *   fus_model_monitor_get   quantity = FUS_MON_*, k in 1..nharm for FUS_MON_COS / FUS_MON_SIN (ignored otherwise);
+ *                           out = T[ndofs] in caller numbering, host or device memory (`space`).  FUS_ERR_STATE
+ *                           while n == 0 or the monitor is off.  The accumulators are not altered: sampling may
+ *                           continue afterwards
+ *   fus_model_monitor_info  number of samples so far, times of the first and the last one (each may be NULL; the
+ *                           times are 0 while n == 0).  FUS_ERR_STATE while the monitor is off */
+enum { FUS_MON_MAX = 0, FUS_MON_MIN = 1, FUS_MON_MEAN = 2, FUS_MON_RMS = 3, FUS_MON_COS = 4, FUS_MON_SIN = 5 };
+int fus_model_monitor(fus_model* model, int which, int nharm, double freq, int64_t skip, int every, int64_t count);
+int fus_model_monitor_get(fus_model* model, int quantity, int k, void* out, int space);
+int fus_model_monitor_info(fus_model* model, int64_t* nsamples, double* t_first, double* t_last);
+
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
 
@@ -306,7 +348,7 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the library's own kernels on the stream they run on.  Names:
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
- * update), "boundary", "halo".  total_ms/count accumulate since the last enable.
+ * update), "boundary", "halo", "monitor" (field-monitor sample).  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

@@ -258,6 +258,32 @@ public:
       *times = t;
     return out;
   }
+  // field monitor (fusmi.h): after every `every`-th step past the first `skip` steps fold u (or v) into per-DOF
+  // running max / min, sum, sum of squares and the cosine / sine sums of the harmonics 1..nharm of freq
+  // (0: the source frequency); every = 0 switches it off
+  void monitor(int which = FUS_U, int nharm = 0, double freq = 0.0, std::int64_t skip = 0, int every = 1,
+               std::int64_t count = 0)
+  {
+    check(fus_model_monitor(h_, which, nharm, freq, skip, every, count));
+  }
+  // quantity = FUS_MON_MAX | MIN | MEAN | RMS | COS | SIN (k = 1..nharm for the last two), caller numbering
+  std::vector<T> monitor_get(int quantity, int k = 0) const
+  {
+    std::vector<T> out((size_t)d_->ndofs());
+    check(fus_model_monitor_get(h_, quantity, k, out.data(), FUS_HOST));
+    return out;
+  }
+  struct MonitorInfo
+  {
+    std::int64_t nsamples;
+    double t_first, t_last;
+  };
+  MonitorInfo monitor_info() const
+  {
+    MonitorInfo i{0, 0.0, 0.0};
+    check(fus_model_monitor_info(h_, &i.nsamples, &i.t_first, &i.t_last));
+    return i;
+  }
   fus_model* handle() const { return h_; }
   ~SpectralModel() { fus_model_destroy(h_); }
   SpectralModel(const SpectralModel&) = delete;
