@@ -290,6 +290,16 @@ struct fus_model
   double mon_freq = 0.0;
   int64_t mon_skip = 0, mon_count = 0, mon_step = 0, mon_n = 0;
   double mon_t_first = 0.0, mon_t_last = 0.0;
+  // phased / apodised source (fus_model_set_source).  src_mode 0: the default source, d_bsrc / d_bsrc2 hold the facet
+  // weights.  1: amplitude only -- the weights times the per-entry amplitude, folded in once; the scalar path stays.
+  // 2: delays or a burst -- k_source_entries writes d_bsrc / d_bsrc2 = weights x per-entry waveform for a stage time and
+  // the kernels get gval = dgval = 1.  d_src_base / d_src_base2 keep the unmodified weights, d_src_amp / d_src_tau the
+  // per-entry amplitude and delay, all in boundary-entry order.  src_tn_int / src_tn_sh: the stage time the block-interior
+  // entries [0, nb_int) and the shared entries [nb_int, nb) of d_bsrc hold (NaN: none).
+  int src_mode = 0;
+  void *d_src_base = nullptr, *d_src_base2 = nullptr, *d_src_amp = nullptr, *d_src_tau = nullptr;
+  double src_dur = 0.0;
+  double src_tn_int = NAN, src_tn_sh = NAN;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -1313,6 +1323,30 @@ static StageArgs<T> stage_args(fus_model* m, int i, const StageScalars& sc)
   return S;
 }
 
+// Per-entry source (src_mode 2): the weight arrays of the entries [k0, k1) for the stage time tn.  The rule of the
+// callers: before a kernel reads a range of d_bsrc / d_bsrc2, the range holds the values for the time whose scalar
+// that kernel would have carried -- the block kernel and k_boundary_partial the stage's own time, the shared-dof and
+// interface stage kernels (BndNext) the next stage's.
+template <typename T>
+static int source_entries(fus_model* m, int64_t k0, int64_t k1, double tn)
+{
+  if (k1 <= k0)
+    return FUS_OK;
+  const bool lossy = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
+  const SourceWave W = source_wave_make(m->freq, m->amp, m->speed, (lossy && m->forms == 0) ? 2.0 : 1.0, m->src_dur);
+  ProfScope ps(m->ctx, "source");
+  hipLaunchKernelGGL((k_source_entries<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
+                     static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
+                     static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), W, tn,
+                     static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+  HIPCHK(hipGetLastError());
+  if (k0 == 0)
+    m->src_tn_int = tn;
+  if (k1 == m->nb)
+    m->src_tn_sh = tn;
+  return FUS_OK;
+}
+
 // Stage i, first half: the block kernel applies K(-1/rho) to u_stage and, for every block-interior
 // dof, finishes the stage right away (boundary terms, kv = b/m, axpys); shared dofs leave as partial
 // sums, are reduced into b's shared range, and the interface entries are packed for the exchange.
@@ -1356,6 +1390,19 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   // already overlaps k_shared_stage, and on one GPU with the exchange looped back the extra small
   // launch costs more (2.47 vs 2.41 ms per step at 64^3 p=4) than it hides.  A block's epilogue only writes that block's interior dofs,
   // which no other block and none of the small kernels below reads.
+  // boundary terms of the shared boundary dofs: a launch of their own unless the previous stage left them (below)
+  const int64_t nbs = m->nb - m->nb_int;
+  const StageScalars sc_now = stage_scalars<T>(m, i, t, dt);
+  const bool bnd_launch = nbs > 0 && !(m->bnd_valid && op->bnd_owner == m && m->bnd_tn == sc_now.tn);
+  if (m->src_mode == 2)
+  {
+    // the source rides in the weights: the block-interior entries for this stage's time, the shared ones too when
+    // k_boundary_partial reads them; in the steady RK4 state the previous stage_end has left both
+    S.gval = T(1), S.dgval = T(1);
+    const bool need_int = !(m->src_tn_int == sc_now.tn), need_sh = bnd_launch && !(m->src_tn_sh == sc_now.tn);
+    if (need_int || need_sh)
+      FUSCHK(source_entries<T>(m, need_int ? 0 : m->nb_int, need_sh ? m->nb : m->nb_int, sc_now.tn));
+  }
   const int nb_if = op->L.nblocks_if;
   const bool split = m->ctx->overlap_blocks && !op->neigh.empty() && nb_if > 0 && nb_if < op->L.nblocks;
   {
@@ -1364,9 +1411,7 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   }
   // boundary terms of the shared boundary dofs become one more partial each
   hipStream_t st = m->ctx->stream;
-  const int64_t nbs = m->nb - m->nb_int;
-  const StageScalars sc_now = stage_scalars<T>(m, i, t, dt);
-  if (nbs > 0 && !(m->bnd_valid && op->bnd_owner == m && m->bnd_tn == sc_now.tn))
+  if (bnd_launch)
   {
     ProfScope ps(m->ctx, "boundary");
     hipLaunchKernelGGL((k_boundary_partial<T>), dim3(nblk(nbs)), dim3(256), 0, st, nbs,
@@ -1433,6 +1478,15 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     B.partial = static_cast<T*>(op->d_partial);
     m->bnd_valid = true, m->bnd_tn = scn.tn;
     op->bnd_owner = m;
+    if (m->src_mode == 2)
+    {
+      // the kernels below read the shared entries for the next stage's time; the same launch leaves the
+      // block-interior entries for the next stage's block kernel (this stage's has run: same stream)
+      B.gnext = T(1), B.dgnext = T(1);
+      const bool need_int = !(m->src_tn_int == scn.tn);
+      if (need_int || !(m->src_tn_sh == scn.tn))
+        FUSCHK(source_entries<T>(m, need_int ? 0 : m->nb_int, m->nb, scn.tn));
+    }
   }
   const LeanRK<T> R{(T)sc.b0dt, (T)sc.pdt, T(1) / T(3)};
   const int kind = stage_kind(m, i);
@@ -1990,6 +2044,134 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
     HIPCHK(hipMemsetAsync(op->d_tmp_x, 0, (size_t)n * sizeof(T), st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+// ---- phased / apodised source (fusmi.h) ----
+static void source_free(fus_model* m)
+{
+  for (void** q : {&m->d_src_base, &m->d_src_base2, &m->d_src_amp, &m->d_src_tau})
+  {
+    if (*q)
+      (void)hipFree(*q);
+    *q = nullptr;
+  }
+}
+
+template <typename T>
+static int model_set_source(fus_model* m, const void* amplitude, const void* delay, double duration, int space)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t nb = m->nb;
+  const size_t bytes = (size_t)nb * sizeof(T);
+  HIPCHK(hipStreamSynchronize(st));
+  // (not a hot path: every copy on the model's stream, complete on return)
+  auto copy = [&](void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) -> int
+  {
+    HIPCHK(hipMemcpyAsync(dst, src, nbytes, kind, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FUS_OK;
+  };
+  auto changed = [&]()
+  {
+    m->bnd_valid = false;   // the pseudo boundary partials carry the old source
+    m->gsteps = 0;          // the next step runs directly, as after fus_model_set
+    m->src_tn_int = m->src_tn_sh = NAN;
+  };
+  if (!amplitude && !delay && duration == 0.0)
+  {
+    // the default source: the facet weights go back where the kernels read them
+    if (m->d_src_base)
+    {
+      if (nb > 0)
+        FUSCHK(copy(m->d_bsrc, m->d_src_base, bytes, hipMemcpyDeviceToDevice));
+      if (nb > 0 && m->d_bsrc2)
+        FUSCHK(copy(m->d_bsrc2, m->d_src_base2, bytes, hipMemcpyDeviceToDevice));
+      source_free(m);
+    }
+    m->src_mode = 0, m->src_dur = 0.0;
+    changed();
+    return FUS_OK;
+  }
+  if (!source_duration_ok(m->freq, duration))
+    return fail(FUS_ERR_ARG, "fus_model_set_source: duration is 0 (continuous) or at least two ramp lengths, 8 / freq");
+  // the facet weights and the entries' internal indices, as the setup left them
+  std::vector<int32_t> bidx(nb);
+  std::vector<T> base(nb), base2(m->d_bsrc2 ? nb : 0);
+  if (nb > 0)
+  {
+    FUSCHK(copy(bidx.data(), m->d_bidx, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FUSCHK(copy(base.data(), m->d_src_base ? m->d_src_base : m->d_bsrc, bytes, hipMemcpyDeviceToHost));
+    if (m->d_bsrc2)
+      FUSCHK(copy(base2.data(), m->d_src_base2 ? m->d_src_base2 : m->d_bsrc2, bytes, hipMemcpyDeviceToHost));
+  }
+  // caller vectors on the host
+  std::vector<T> hbuf[2];
+  const T* h[2] = {static_cast<const T*>(amplitude), static_cast<const T*>(delay)};
+  for (int j = 0; j < 2; ++j)
+    if (h[j] && space == FUS_DEVICE)
+    {
+      hbuf[j].resize(op->ndofs);
+      FUSCHK(copy(hbuf[j].data(), h[j], (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost));
+      h[j] = hbuf[j].data();
+    }
+  // gather through dof_perm into boundary-entry order; only the entries with a source weight count
+  std::vector<int32_t> caller(op->L.n_internal, -1);
+  for (int64_t d = 0; d < op->ndofs; ++d)
+    caller[op->L.dof_perm[d]] = (int32_t)d;
+  std::vector<T> amp(nb, T(0)), tau(nb, T(0));
+  for (int64_t k = 0; k < nb; ++k)
+  {
+    if (base[k] == T(0) && (base2.empty() || base2[k] == T(0)))
+      continue;
+    const int32_t d = caller[bidx[k]];
+    const T a = h[0] ? h[0][d] : T(1), td = h[1] ? h[1][d] : T(0);
+    if (!std::isfinite((double)a) || a < T(0) || !std::isfinite((double)td) || td < T(0))
+      return fail(FUS_ERR_ARG, "fus_model_set_source: negative or non-finite amplitude / delay at dof " + std::to_string(d)
+                                   + " of the source boundary");
+    amp[k] = a, tau[k] = td;
+  }
+  // from here on the model changes
+  if (!m->d_src_base)
+  {
+    HIPCHK(hipMalloc(&m->d_src_base, std::max<size_t>(bytes, 16)));
+    if (nb > 0)
+      FUSCHK(copy(m->d_src_base, m->d_bsrc, bytes, hipMemcpyDeviceToDevice));
+    if (m->d_bsrc2)
+    {
+      HIPCHK(hipMalloc(&m->d_src_base2, std::max<size_t>(bytes, 16)));
+      if (nb > 0)
+        FUSCHK(copy(m->d_src_base2, m->d_bsrc2, bytes, hipMemcpyDeviceToDevice));
+    }
+  }
+  if (!delay && duration == 0.0)
+  {
+    // amplitude only: folded into the weights once, the scalar path stays
+    std::vector<T> w(nb), w2(base2.size());
+    for (int64_t k = 0; k < nb; ++k)
+      w[k] = base[k] * amp[k];
+    for (size_t k = 0; k < base2.size(); ++k)
+      w2[k] = base2[k] * amp[k];
+    if (nb > 0)
+      FUSCHK(copy(m->d_bsrc, w.data(), bytes, hipMemcpyHostToDevice));
+    if (nb > 0 && m->d_bsrc2)
+      FUSCHK(copy(m->d_bsrc2, w2.data(), bytes, hipMemcpyHostToDevice));
+    m->src_mode = 1, m->src_dur = 0.0;
+  }
+  else
+  {
+    for (void** q : {&m->d_src_amp, &m->d_src_tau})
+      if (!*q)
+        HIPCHK(hipMalloc(q, std::max<size_t>(bytes, 16)));
+    if (nb > 0)
+    {
+      FUSCHK(copy(m->d_src_amp, amp.data(), bytes, hipMemcpyHostToDevice));
+      FUSCHK(copy(m->d_src_tau, tau.data(), bytes, hipMemcpyHostToDevice));
+    }
+    m->src_mode = 2, m->src_dur = duration;
+  }
+  changed();
   return FUS_OK;
 }
 
@@ -2814,6 +2996,7 @@ int fus_model_destroy(fus_model* m)
     (void)hipFree(q);
   if (m->d_mon)
     (void)hipFree(m->d_mon);
+  source_free(m);
   delete m;
   return FUS_OK;
 }
@@ -3172,6 +3355,18 @@ int fus_model_set(fus_model* m, int which, const void* in, int space)
   return m->op->dtype == FUS_F64
              ? model_getset<double>(m, which, const_cast<void*>(in), space, true)
              : model_getset<float>(m, which, const_cast<void*>(in), space, true);
+}
+
+// ---- phased / apodised source (fusmi.h) ----
+int fus_model_set_source(fus_model* m, const void* amplitude, const void* delay, double duration, int space)
+{
+  if (!m || (space != FUS_HOST && space != FUS_DEVICE) || !(duration >= 0.0))
+    return fail(FUS_ERR_ARG, "fus_model_set_source: bad model, space or duration");
+  if (!m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_set_source: the model's setup is not finished");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  return m->op->dtype == FUS_F64 ? model_set_source<double>(m, amplitude, delay, duration, space)
+                                 : model_set_source<float>(m, amplitude, delay, duration, space);
 }
 
 int fus_model_get_mass(fus_model* m, void* out)

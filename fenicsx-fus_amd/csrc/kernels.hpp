@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "geom.hpp"
+#include "source_wave.hpp"
 
 namespace fus
 {
@@ -3689,6 +3690,33 @@ __global__ void k_unpack_ordered(int64_t nu, const int32_t* __restrict__ uidx,
     acc += (sidx < 0) ? own : recvbuf[sidx];
   }
   vec[u] = acc;
+}
+
+// ---- phased / apodised source (fus_model_set_source, fusmi.h) ---------------------------------------------------
+// The block kernel and the shared-dof kernels read the source as  gval * bnd_src[k] (+ dgval * bnd_src2[k]).  A source
+// with its own time history per entry keeps those kernels as they are: this kernel evaluates the waveform of
+// source_wave.hpp per boundary entry into the weight arrays they read,
+//   out[k] = base[k] g_k(t),   out2[k] = base2[k] dg_k(t)   (base2 / out2 only where the model has a dg term),
+// for the entries [k0, k1), and the scalars are passed as 1.  base / base2 are the facet weights as the setup left
+// them, amp / tau the per-entry amplitude and delay.  An entry without a source weight (a pure absorbing entry)
+// stores zeros and evaluates nothing.  One thread per entry, every access at k; the waveform in double, rounded
+// to T on store.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_source_entries(int64_t k0, int64_t k1, const T* __restrict__ base, const T* __restrict__ base2,
+                 const T* __restrict__ amp, const T* __restrict__ tau, const SourceWave W, double t,
+                 T* __restrict__ out, T* __restrict__ out2)
+{
+  const int64_t k = k0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= k1)
+    return;
+  const double b = (double)base[k], b2 = base2 ? (double)base2[k] : 0.0;
+  double g = 0.0, dg = 0.0;
+  if (b != 0.0 || b2 != 0.0)
+    source_wave(W, (double)amp[k], t - (double)tau[k], &g, &dg);
+  out[k] = (T)(b * g);
+  if (out2)
+    out2[k] = (T)(b2 * dg);
 }
 
 } // namespace fus

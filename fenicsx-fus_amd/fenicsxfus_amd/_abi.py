@@ -29,6 +29,7 @@ SYMBOLS = [
     "fus_model_stage_begin", "fus_model_stage_end",
     "fus_model_set_receivers", "fus_model_sample", "fus_model_record", "fus_model_get_records",
     "fus_model_monitor", "fus_model_monitor_get", "fus_model_monitor_info",
+    "fus_model_set_source",
 ]
 
 

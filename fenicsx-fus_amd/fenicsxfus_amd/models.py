@@ -200,6 +200,23 @@ class _SpectralExplicit:
                                           ptr(f.x.array), C.c_int(_abi.FUS_HOST)))
         return f
 
+    # ---- phased / apodised source: per-DOF amplitude and delay, optional tone burst (fusmi.h) ----
+    def set_source(self, amplitude=None, delay=None, duration: float = 0.0):
+        """Give every DOF of the source boundary (tag 1) its own amplitude factor (>= 0, default 1) and time delay
+        (>= 0, default 0): the source there is ``amplitude * g(t - delay)``, 0 until ``t = delay``.  ``duration`` > 0
+        makes it a tone burst that ramps down over its last four periods (at least eight periods long).  Arrays or
+        Functions over the model's space; values off the source boundary are ignored (see
+        :mod:`fenicsxfus_amd.source` for focusing and steering delays).  All defaults: :meth:`clear_source`."""
+        a, d = (None if x is None else np.ascontiguousarray(_array(x), dtype=self.data.dtype) for x in (amplitude, delay))
+        for x in (a, d):
+            if x is not None and x.shape != (self.data.ndofs,):
+                raise _abi.FusError(f"set_source: expected {self.data.ndofs} values, one per DOF, got shape {x.shape}")
+        check(lib().fus_model_set_source(self.h, ptr(a), ptr(d), C.c_double(duration), C.c_int(_abi.FUS_HOST)))
+
+    def clear_source(self):
+        """Back to the default source: the same g(t) at every DOF of the source boundary."""
+        check(lib().fus_model_set_source(self.h, None, None, C.c_double(0.0), C.c_int(_abi.FUS_HOST)))
+
     def u_sol(self):
         self._pull()
         return self.u_n

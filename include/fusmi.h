@@ -318,6 +318,37 @@ int fus_model_monitor(fus_model* model, int which, int nharm, double freq, int64
 int fus_model_monitor_get(fus_model* model, int quantity, int k, void* out, int space);
 int fus_model_monitor_info(fus_model* model, int64_t* nsamples, double* t_first, double* t_last);
 
+/* ---- phased and apodised sources: per-DOF amplitude, delay and tone burst -----------------------------------------
+ * The reference's source is one scalar g(t) times the diagonal facet weights of the tag-1 boundary (Linear.hpp:185-192,
+ * :204-205), so every DOF of that boundary radiates with the same amplitude and phase.  This call gives each DOF d of it
+ * an amplitude factor a_d >= 0 and a delay tau_d >= 0 -- electronic focusing and steering of a flat aperture, as array
+ * transducers do it -- and optionally makes the source a tone burst.
+ *
+ * Waveform.  With the local time s = t - tau_d, the source frequency f, w0 = 2 pi f, the ramp length Lr = 4 / f (the
+ * reference's window_length), the duration D (0 = continuous) and C = scale p0 w0 / s0 (scale = 2 for FUS_LOSSY /
+ * FUS_WESTERVELT with option "forms" = 0, else 1, as for the default source):
+ *   W(s)  = 0                                  for s <= 0, and for s >= D when D > 0
+ *         = (1 - cos(pi f s / 4)) / 2          for 0 < s < Lr
+ *         = (1 - cos(pi f (D - s) / 4)) / 2    for D - Lr < s < D when D > 0
+ *         = 1                                  otherwise
+ *   g_d(t)  = a_d C W(s) cos(w0 s)
+ *   dg_d(t) = a_d C (W'(s) cos(w0 s) - W(s) w0 sin(w0 s))       (the dg term of FUS_LOSSY / FUS_WESTERVELT)
+ * The source of a DOF is exactly 0 for t <= tau_d (and for t >= tau_d + D), so nothing radiates before its delay has
+ * passed.  With a = 1, tau = 0, D = 0 and t >= 0 this is the default source.  Evaluated in double for both scalar types
+ * at the stage time the default source uses, rounded to T with the facet weight.
+ *   amplitude, delay   T[ndofs] in caller numbering, host or device memory (`space`); NULL = 1 everywhere / 0 everywhere.
+ *                      Values at DOFs off the source boundary are ignored; a negative or non-finite value at a DOF on
+ *                      it -> FUS_ERR_ARG, the source stays as it was
+ *   duration           D: 0 or >= 2 Lr = 8 / f; 0 < D < 2 Lr (the ramps would overlap) -> FUS_ERR_ARG
+ * amplitude == NULL, delay == NULL, duration == 0 restores the default source and frees the arrays.  Amplitude only
+ * (delay == NULL, duration == 0): the amplitude is folded into the facet weights once and a step enqueues what it
+ * always did.  Otherwise one small kernel launch per new stage time (classical RK4: two per step, its two middle
+ * stages share a time and its last one the next step's first) writes weight x g_d(stage time) for the boundary
+ * entries -- profile name "source" -- and the stage kernels run unchanged.
+ * Legal once the model's setup is finished (FUS_ERR_STATE before) and between steps; the state is kept.  Several ranks:
+ * every sharer of a DOF passes the same values for it (they are functions of position). */
+int fus_model_set_source(fus_model* model, const void* amplitude, const void* delay, double duration, int space);
+
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
 
@@ -348,7 +379,7 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the library's own kernels on the stream they run on.  Names:
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
- * update), "boundary", "halo", "monitor" (field-monitor sample).  total_ms/count accumulate since the last enable.
+ * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform).  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

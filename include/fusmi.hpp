@@ -284,6 +284,12 @@ public:
     check(fus_model_monitor_info(h_, &i.nsamples, &i.t_first, &i.t_last));
     return i;
   }
+  // phased / apodised source (fusmi.h): amplitude factor and delay per DOF (T[ndofs], caller numbering; nullptr = 1 / 0)
+  // and the burst duration (0: continuous); all defaults restore the uniform source
+  void set_source(const T* amp, const T* delay, double duration = 0.0)
+  {
+    check(fus_model_set_source(h_, amp, delay, duration, FUS_HOST));
+  }
   fus_model* handle() const { return h_; }
   ~SpectralModel() { fus_model_destroy(h_); }
   SpectralModel(const SpectralModel&) = delete;
