@@ -300,6 +300,9 @@ struct fus_model
   void *d_src_base = nullptr, *d_src_base2 = nullptr, *d_src_amp = nullptr, *d_src_tau = nullptr;
   double src_dur = 0.0;
   double src_tn_int = NAN, src_tn_sh = NAN;
+  // c0 and rho0 as fus_model_create was given them, internal cell order: fus_thermal_set_heat_from_monitor forms
+  // q_coef = 2 alpha / (rho c) from them
+  void *d_c0 = nullptr, *d_rho0 = nullptr;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -1008,10 +1011,11 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
 
   // operator coefficients -1/rho (Linear.hpp:154-155) [and -delta/(rho c^2), Lossy.hpp:166-169]
   // and the mass coefficient 1/(rho c^2) (forms.py:36), internal element order
-  std::vector<T> coef(op->ncells), coef2(lossy ? op->ncells : 0), mcoef(op->ncells);
+  std::vector<T> coef(op->ncells), coef2(lossy ? op->ncells : 0), mcoef(op->ncells), c0i(op->ncells), rho0i(op->ncells);
   for (int64_t e = 0; e < op->ncells; ++e)
   {
     const int64_t cell = L.cell_perm[e];
+    c0i[e] = c0[cell], rho0i[e] = rho0[cell];
     coef[e] = T(-1.0) / rho0[cell];
     if (lossy)
       coef2[e] = -delta0[cell] / rho0[cell] / c0[cell] / c0[cell];
@@ -1023,6 +1027,10 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
     FUSCHK(upload(pool, &d_coef2, coef2, st));
   FUSCHK(upload(pool, &d_mcoef, mcoef, st));
   m->coef = d_coef, m->coef2 = d_coef2;
+  T *d_c0i, *d_rho0i;
+  FUSCHK(upload(pool, &d_c0i, c0i, st));
+  FUSCHK(upload(pool, &d_rho0i, rho0i, st));
+  m->d_c0 = d_c0i, m->d_rho0 = d_rho0i;
 
   // lumped mass, this rank's cells only: m = M(1/(rho c^2)) 1  (Linear.hpp:127-133)
   T* ones = static_cast<T*>(m->un);
@@ -1628,6 +1636,9 @@ struct DegreeImpl
                      const int32_t*, const int32_t*, const int32_t*);
   int (*model_step)(fus_model*, double, double);
   int (*stage_begin)(fus_model*, int, double, double);
+  // b = A(coef) x on device vectors in internal numbering, coef in internal cell order (apply_internal: the plain
+  // operator action op_apply runs, without its renumbering passes); kind = OP_STIFFNESS | OP_MASS
+  int (*apply_int)(fus_op*, int, const void*, const void*, void*);
 };
 #define FUS_CAT_(a, b) a##b
 #define FUS_CAT(a, b) FUS_CAT_(a, b)
@@ -1640,10 +1651,18 @@ static int op_apply_kind(fus_op* op, int kind, const void* x, const void* cf, vo
                               : op_apply<T, P, OP_MASS>(op, x, cf, y, space);
 }
 template <typename T, int P>
+static int apply_int_kind(fus_op* op, int kind, const void* cf, const void* x, void* b)
+{
+  return kind == OP_STIFFNESS
+             ? apply_internal<T, P, OP_STIFFNESS>(op, static_cast<const T*>(cf), static_cast<const T*>(x), static_cast<T*>(b))
+             : apply_internal<T, P, OP_MASS>(op, static_cast<const T*>(cf), static_cast<const T*>(x), static_cast<T*>(b));
+}
+template <typename T, int P>
 static DegreeImpl make_degree_impl()
 {
   return {&op_setup_device<T, P>, &op_apply_kind<T, P>, &op_get_geometry<T, P>,
-          &model_setup<T, P>,     &model_step<T, P>,    &stage_begin<T, P>};
+          &model_setup<T, P>,     &model_step<T, P>,    &stage_begin<T, P>,
+          &apply_int_kind<T, P>};
 }
 // one unit per (degree, scalar type): -DFUS_TU_DEGREE=k -DFUS_TU_DTYPE=64|32
 #if FUS_TU_DTYPE == 64
@@ -1706,6 +1725,11 @@ static int d_op_apply(fus_op* op, int kind, const void* x, const void* cf, void*
 {
   FUS_DEGREE(d, op->dtype, op->P);
   return d->op_apply(op, kind, x, cf, y, space);
+}
+static int d_apply_int(fus_op* op, int kind, const void* cf, const void* x, void* b)
+{
+  FUS_DEGREE(d, op->dtype, op->P);
+  return d->apply_int(op, kind, cf, x, b);
 }
 static int d_op_get_geometry(fus_op* op, void* G, void* dJ)
 {
@@ -2044,6 +2068,332 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
     HIPCHK(hipMemsetAsync(op->d_tmp_x, 0, (size_t)n * sizeof(T), st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+// ---- Pennes bioheat model and CEM43 dose (fusmi.h "bioheat") ----
+// The operator action runs through apply_internal (STAGE_NONE block kernel + shared reduction) on the thermal object's
+// own vectors; of the op's scratch it takes d_partial (rewritten by every operator pass of any model; the wave models'
+// pseudo boundary slots behind n_partial are not touched), d_tmp_c and d_tmp_coef -- never d_tmp_x, whose padding
+// therefore stays zero.
+struct fus_thermal
+{
+  fus_ctx* ctx = nullptr;
+  fus_op* op = nullptr;
+  double t_base = 37.0;
+  // n_internal vectors of T: rise theta_0, stage input, accumulator, operator result, 1 / m_C, m_C, m_W, heat load h
+  void *th0 = nullptr, *ths = nullptr, *acc = nullptr, *b = nullptr, *minv = nullptr, *mc = nullptr, *mw = nullptr,
+       *h = nullptr;
+  void *kneg = nullptr;        // -k per cell, internal cell order
+  double* dose = nullptr;      // CEM43 minutes, n_internal doubles
+  double* d_stage = nullptr;   // ndofs doubles in caller numbering (dose in / out)
+  std::vector<void*> allocs;
+  bool initialised = false;
+};
+
+template <typename T>
+static int thermal_cells_to_internal(fus_thermal* th, const void* host_cells, T* out_i)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  T* cc = static_cast<T*>(op->d_tmp_coef);
+  HIPCHK(hipMemcpyAsync(cc, host_cells, op->ncells * sizeof(T), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL((k_cells_to_internal<T>), dim3(nblk(op->ncells)), dim3(256), 0, st, op->ncells, op->d_cell_perm,
+                     static_cast<const T*>(cc), out_i);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // host_cells may be a temporary of the caller
+  return FUS_OK;
+}
+
+// out = M(coef_i) 1 (coef_i in internal cell order); acc serves as the vector of ones and is zeroed again
+template <typename T>
+static int thermal_lumped(fus_thermal* th, const T* coef_i, T* out)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal;
+  hipLaunchKernelGGL((k_fill<T>), dim3(1024), dim3(256), 0, st, n, static_cast<T*>(th->acc), T(1));
+  HIPCHK(hipMemsetAsync(out, 0, n * sizeof(T), st));
+  FUSCHK(d_apply_int(op, OP_MASS, coef_i, th->acc, out));
+  HIPCHK(hipMemsetAsync(th->acc, 0, n * sizeof(T), st));
+  return FUS_OK;
+}
+
+template <typename T>
+static int thermal_setup(fus_thermal* th, const void* k_, const void* rc_, const void* w_)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal, nc = op->ncells;
+  const T *kc = static_cast<const T*>(k_), *rc = static_cast<const T*>(rc_), *wc = static_cast<const T*>(w_);
+  for (int64_t e = 0; e < nc; ++e)
+  {
+    if (!(rc[e] > T(0)) || !std::isfinite((double)rc[e]))
+      return fail(FUS_ERR_ARG, "fus_thermal_create: rho_c must be positive and finite in every cell");
+    if (!(kc[e] >= T(0)) || !std::isfinite((double)kc[e]))
+      return fail(FUS_ERR_ARG, "fus_thermal_create: conductivity must be >= 0 and finite in every cell");
+    if (wc && (!(wc[e] >= T(0)) || !std::isfinite((double)wc[e])))
+      return fail(FUS_ERR_ARG, "fus_thermal_create: perfusion must be >= 0 and finite in every cell");
+  }
+  for (void** v : {&th->th0, &th->ths, &th->acc, &th->b, &th->minv, &th->mc, &th->mw, &th->h})
+    FUSCHK(dalloc_bytes(th->allocs, v, n * sizeof(T), true, st));
+  void* dz = nullptr;
+  FUSCHK(dalloc_bytes(th->allocs, &dz, n * sizeof(double), true, st));
+  th->dose = static_cast<double*>(dz);
+  FUSCHK(dalloc_bytes(th->allocs, &dz, op->ndofs * sizeof(double), true, st));
+  th->d_stage = static_cast<double*>(dz);
+  FUSCHK(dalloc_bytes(th->allocs, &th->kneg, nc * sizeof(T), false, st));
+  T* ci = static_cast<T*>(th->kneg);   // per-cell staging until -k takes it
+  FUSCHK(thermal_cells_to_internal<T>(th, rc, ci));
+  FUSCHK(thermal_lumped<T>(th, ci, static_cast<T*>(th->mc)));
+  hipLaunchKernelGGL((k_reciprocal<T>), dim3(nblk(n)), dim3(256), 0, st, n, static_cast<const T*>(th->mc),
+                     static_cast<T*>(th->minv));
+  if (wc)
+  {
+    FUSCHK(thermal_cells_to_internal<T>(th, wc, ci));
+    FUSCHK(thermal_lumped<T>(th, ci, static_cast<T*>(th->mw)));
+  }
+  std::vector<T> kn(nc);
+  for (int64_t e = 0; e < nc; ++e)
+    kn[e] = -kc[e];
+  FUSCHK(thermal_cells_to_internal<T>(th, kn.data(), ci));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+template <typename T>
+static unsigned thermal_grid(const fus_thermal* th, int64_t* nvec)
+{
+  *nvec = th->op->L.n_internal / (16 / (int64_t)sizeof(T));
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((*nvec + 255) / 256, (int64_t)th->ctx->num_cus * 8));
+}
+
+// one classical RK4 step (a = 0, 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6): per stage the operator's two launches and
+// k_thermal_stage
+template <typename T>
+static int thermal_step(fus_thermal* th, double dt_, double sigma)
+{
+  fus_op* op = th->op;
+  const T dt = (T)dt_;
+  const T a_next[4] = {T(0.5), T(0.5), T(1), T(0)};
+  const T b_runge[4] = {(T)(1.0 / 6.0), (T)(1.0 / 3.0), (T)(1.0 / 3.0), (T)(1.0 / 6.0)};
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec);
+  for (int i = 0; i < 4; ++i)
+  {
+    const T* x = static_cast<const T*>(i == 0 ? th->th0 : th->ths);
+    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, x, th->b));
+    ThermalStage<T> A;
+    A.b = static_cast<const T*>(th->b), A.th_in = x;
+    A.th_out = static_cast<T*>(i == 3 ? th->th0 : th->ths);
+    A.th0 = static_cast<const T*>(th->th0), A.acc = static_cast<T*>(th->acc);
+    A.minv = static_cast<const T*>(th->minv), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+    A.dose = th->dose;
+    A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
+    A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
+    ProfScope ps(th->ctx, "thermal");
+    if (i == 0)
+      hipLaunchKernelGGL((k_thermal_stage<T, 0>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    else if (i < 3)
+      hipLaunchKernelGGL((k_thermal_stage<T, 1>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    else
+      hipLaunchKernelGGL((k_thermal_stage<T, 3>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    HIPCHK(hipGetLastError());
+  }
+  return FUS_OK;
+}
+
+// h = M(qcoef_i) 1 .* q: q a T vector in internal numbering (q_i), or Q / nsamp from the monitor's plane (Q)
+template <typename T>
+static int thermal_heat(fus_thermal* th, const T* qcoef_i, const T* q_i, const double* Q, double nsamp)
+{
+  fus_op* op = th->op;
+  T* mq = static_cast<T*>(th->b);
+  FUSCHK(thermal_lumped<T>(th, qcoef_i, mq));
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec);
+  hipLaunchKernelGGL((k_thermal_heat<T>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, static_cast<const T*>(mq), q_i, Q,
+                     nsamp, static_cast<T*>(th->h));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(th->b, 0, op->L.n_internal * sizeof(T), th->ctx->stream));
+  HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  return FUS_OK;
+}
+
+template <typename T>
+static int thermal_set_heat(fus_thermal* th, const void* q, const void* q_coef, int space)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal, nc = op->ncells;
+  if (!q)
+  {
+    HIPCHK(hipMemsetAsync(th->h, 0, n * sizeof(T), st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FUS_OK;
+  }
+  T* cc = static_cast<T*>(op->d_tmp_coef);
+  T* ci = cc + nc;
+  if (!q_coef)
+    hipLaunchKernelGGL((k_fill<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, ci, T(1));
+  else
+  {
+    const T* src = static_cast<const T*>(q_coef);
+    if (space == FUS_HOST)
+    {
+      HIPCHK(hipMemcpyAsync(cc, q_coef, nc * sizeof(T), hipMemcpyHostToDevice, st));
+      src = cc;
+    }
+    hipLaunchKernelGGL((k_cells_to_internal<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, op->d_cell_perm, src, ci);
+  }
+  // q in internal numbering: the stage input's place is free between steps (its padding stays zero)
+  const T* qs = static_cast<const T*>(q);
+  T* tc = static_cast<T*>(op->d_tmp_c);
+  if (space == FUS_HOST)
+  {
+    HIPCHK(hipMemcpyAsync(tc, q, op->ndofs * sizeof(T), hipMemcpyHostToDevice, st));
+    qs = tc;
+  }
+  T* qi = static_cast<T*>(th->ths);
+  hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(op->ndofs)), dim3(256), 0, st, op->ndofs, op->d_dof_perm, qs, qi);
+  HIPCHK(hipGetLastError());
+  FUSCHK(thermal_heat<T>(th, ci, qi, nullptr, 1.0));
+  HIPCHK(hipMemsetAsync(th->ths, 0, n * sizeof(T), st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+template <typename T>
+static int thermal_heat_from_monitor(fus_thermal* th, fus_model* m, const void* absorption)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal, nc = op->ncells;
+  const T* al = static_cast<const T*>(absorption);
+  for (int64_t e = 0; e < nc; ++e)
+    if (!(al[e] >= T(0)) || !std::isfinite((double)al[e]))
+      return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_monitor: absorption must be >= 0 and finite in every cell");
+  T* cc = static_cast<T*>(op->d_tmp_coef);
+  T* ci = cc + nc;
+  HIPCHK(hipMemcpyAsync(cc, al, nc * sizeof(T), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL((k_cells_to_internal<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, op->d_cell_perm,
+                     static_cast<const T*>(cc), ci);
+  hipLaunchKernelGGL((k_thermal_qcoef<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, static_cast<const T*>(ci),
+                     static_cast<const T*>(m->d_rho0), static_cast<const T*>(m->d_c0), cc);
+  HIPCHK(hipGetLastError());
+  const double* Q = reinterpret_cast<const double*>(static_cast<const T*>(m->d_mon) + 2 * n) + n;   // acc plane 1
+  return thermal_heat<T>(th, cc, nullptr, Q, (double)m->mon_n);
+}
+
+template <typename T>
+static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space, bool set)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t nd = op->ndofs;
+  if (which == FUS_TH_DOSE)
+  {
+    double* stg = th->d_stage;
+    if (set)
+    {
+      const double* src = static_cast<const double*>(host_or_dev);
+      if (space == FUS_HOST)
+      {
+        HIPCHK(hipMemcpyAsync(stg, host_or_dev, nd * sizeof(double), hipMemcpyHostToDevice, st));
+        src = stg;
+      }
+      hipLaunchKernelGGL((k_to_internal<double>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, src, th->dose);
+    }
+    else
+    {
+      double* dst = space == FUS_HOST ? stg : static_cast<double*>(host_or_dev);
+      hipLaunchKernelGGL((k_from_internal<double, 0>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm,
+                         static_cast<const double*>(th->dose), dst);
+      if (space == FUS_HOST)
+        HIPCHK(hipMemcpyAsync(host_or_dev, stg, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+  }
+  else
+  {
+    T* vec = static_cast<T*>(which == FUS_TH_RISE ? th->th0 : th->h);
+    T* tc = static_cast<T*>(op->d_tmp_c);
+    if (set)
+    {
+      const T* src = static_cast<const T*>(host_or_dev);
+      if (space == FUS_HOST)
+      {
+        HIPCHK(hipMemcpyAsync(tc, host_or_dev, nd * sizeof(T), hipMemcpyHostToDevice, st));
+        src = tc;
+      }
+      hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, src, vec);
+    }
+    else
+    {
+      T* dst = space == FUS_HOST ? tc : static_cast<T*>(host_or_dev);
+      hipLaunchKernelGGL((k_from_internal<T, 0>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm,
+                         static_cast<const T*>(vec), dst);
+      if (space == FUS_HOST)
+        HIPCHK(hipMemcpyAsync(host_or_dev, tc, nd * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+// Power iteration for lambda_max of m_C^-1 (K(k) + diag m_W).  Setup-time work: the operator and the quotient
+// y = (K(k) x + m_W x) / m_C run on the device, y is pulled, the three m_C-weighted dot products and the normalisation
+// are done on the host in double, and the next x is pushed back.
+template <typename T>
+static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal, nd = op->ndofs;
+  std::vector<T> xc(nd);
+  for (int64_t d = 0; d < nd; ++d)
+    xc[d] = (T)(1.0 + 0.5 * std::sin(37.0 * (double)d + 1.0));
+  T* tc = static_cast<T*>(op->d_tmp_c);
+  T* xd = static_cast<T*>(th->ths);   // the stage input's place is free between steps
+  T* yd = static_cast<T*>(th->acc);
+  HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(T), st));
+  HIPCHK(hipMemcpyAsync(tc, xc.data(), nd * sizeof(T), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, static_cast<const T*>(tc), xd);
+  std::vector<T> x(n), y(n), mc(n);
+  HIPCHK(hipMemcpyAsync(x.data(), xd, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(mc.data(), th->mc, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  double rho = 0.0;
+  for (int it = 0; it < iters; ++it)
+  {
+    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, xd, th->b));
+    hipLaunchKernelGGL((k_thermal_power<T>), dim3(1024), dim3(256), 0, st, n, static_cast<const T*>(th->b),
+                       static_cast<const T*>(xd), static_cast<const T*>(th->mw), static_cast<const T*>(th->minv), yd);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(y.data(), yd, n * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double xy = 0.0, xx = 0.0, yy = 0.0;
+    for (int64_t i = 0; i < n; ++i)
+    {
+      const double m = (double)mc[i], xi = (double)x[i], yi = (double)y[i];
+      xy += xi * (m * yi), xx += xi * (m * xi), yy += yi * (m * yi);
+    }
+    if (!(xx > 0.0) || !std::isfinite(xy) || !std::isfinite(yy))
+      return fail(FUS_ERR_STATE, "fus_thermal_lambda_max: the iteration broke down (zero or non-finite vector)");
+    rho = xy / xx;
+    if (!(yy > 0.0))   // k = 0 and W = 0 everywhere: the operator is zero
+      break;
+    const double nrm = std::sqrt(yy);
+    for (int64_t i = 0; i < n; ++i)
+      x[i] = (T)((double)y[i] / nrm);
+    HIPCHK(hipMemcpyAsync(xd, x.data(), n * sizeof(T), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(T), st));
+  HIPCHK(hipMemsetAsync(yd, 0, n * sizeof(T), st));
+  HIPCHK(hipStreamSynchronize(st));
+  *lambda = rho;
   return FUS_OK;
 }
 
@@ -3269,6 +3619,130 @@ int fus_model_monitor_get(fus_model* m, int quantity, int k, void* out, int spac
   HIPCHK(hipSetDevice(m->ctx->device));
   return m->op->dtype == FUS_F64 ? monitor_get<double>(m, quantity, k, out, space)
                                  : monitor_get<float>(m, quantity, k, out, space);
+}
+
+// ---- bioheat (fusmi.h): the typed implementation sits with the monitor's, ahead of the C ABI ----
+#define FUS_TH_CALL(th, fn, ...) ((th)->op->dtype == FUS_F64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
+
+int fus_thermal_create(fus_ctx* c, fus_op* op, const void* conductivity, const void* rho_c, const void* perfusion,
+                       double t_base, fus_thermal** out)
+{
+  if (!c || !op || !conductivity || !rho_c || !out)
+    return fail(FUS_ERR_ARG, "fus_thermal_create: null argument");
+  if (op->ctx != c)
+    return fail(FUS_ERR_ARG, "fus_thermal_create: the operator data belongs to another context");
+  if (!std::isfinite(t_base))
+    return fail(FUS_ERR_ARG, "fus_thermal_create: t_base must be finite");
+  if (!op->neigh.empty() || c->nranks > 1)
+    return fail(FUS_ERR_STATE, "fus_thermal_create: several ranks are not supported (the operator action inside the "
+                               "thermal step does no inter-rank reduction)");
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<fus_thermal> th(new fus_thermal());
+  th->ctx = c, th->op = op, th->t_base = t_base;
+  const int r = FUS_TH_CALL(th, thermal_setup, th.get(), conductivity, rho_c, perfusion);
+  if (r != FUS_OK)
+  {
+    for (void* q : th->allocs)
+      (void)hipFree(q);
+    return r;
+  }
+  *out = th.release();
+  return FUS_OK;
+}
+
+int fus_thermal_destroy(fus_thermal* th)
+{
+  if (!th)
+    return FUS_OK;
+  (void)hipSetDevice(th->ctx->device);
+  (void)hipStreamSynchronize(th->ctx->stream);
+  for (void* q : th->allocs)
+    (void)hipFree(q);
+  delete th;
+  return FUS_OK;
+}
+
+int fus_thermal_init(fus_thermal* th)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_init: null argument");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  const int64_t n = th->op->L.n_internal;
+  for (void* v : {th->th0, th->ths, th->acc})
+    HIPCHK(hipMemsetAsync(v, 0, n * th->op->ts, th->ctx->stream));
+  HIPCHK(hipMemsetAsync(th->dose, 0, n * sizeof(double), th->ctx->stream));
+  HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  th->initialised = true;
+  return FUS_OK;
+}
+
+int fus_thermal_set(fus_thermal* th, int which, const void* in, int space)
+{
+  if (!th || !in || (which != FUS_TH_RISE && which != FUS_TH_DOSE) || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_thermal_set: null argument, which not FUS_TH_RISE | FUS_TH_DOSE, or bad space");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  FUSCHK(FUS_TH_CALL(th, thermal_vec, th, which, const_cast<void*>(in), space, true));
+  th->initialised = true;
+  return FUS_OK;
+}
+
+int fus_thermal_get(fus_thermal* th, int which, void* out, int space)
+{
+  if (!th || !out || which < FUS_TH_RISE || which > FUS_TH_HEAT || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_thermal_get: null argument, which not FUS_TH_RISE | FUS_TH_DOSE | FUS_TH_HEAT, or bad space");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_vec, th, which, out, space, false);
+}
+
+int fus_thermal_set_heat(fus_thermal* th, const void* q, const void* q_coef, int space)
+{
+  if (!th || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat: null argument or bad space");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_set_heat, th, q, q_coef, space);
+}
+
+int fus_thermal_set_heat_from_monitor(fus_thermal* th, fus_model* m, const void* absorption)
+{
+  if (!th || !m || !absorption)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_monitor: null argument");
+  if (m->op != th->op)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_monitor: the model runs on another fus_op than the thermal object");
+  if (m->mon_every <= 0 || !m->d_mon)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the model's monitor is off (fus_model_monitor)");
+  if (m->mon_which != FUS_U)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the monitor watches FUS_V; the heat needs the pressure, FUS_U");
+  if (m->mon_n == 0)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the monitor has taken no sample yet");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_heat_from_monitor, th, m, absorption);
+}
+
+int fus_thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
+{
+  if (!th || !lambda)
+    return fail(FUS_ERR_ARG, "fus_thermal_lambda_max: null argument");
+  if (iters < 1)
+    return fail(FUS_ERR_ARG, "fus_thermal_lambda_max: iters must be at least 1");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_lambda_max, th, iters, lambda);
+}
+
+int fus_thermal_steps(fus_thermal* th, double dt, int64_t nsteps, double heat_scale)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_steps: null argument");
+  if (!(dt > 0) || !std::isfinite(dt))
+    return fail(FUS_ERR_ARG, "fus_thermal_steps: dt must be positive and finite");
+  if (nsteps < 0 || !std::isfinite(heat_scale))
+    return fail(FUS_ERR_ARG, "fus_thermal_steps: nsteps must be >= 0 and heat_scale finite");
+  if (!th->initialised)
+    return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called before fus_thermal_steps");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  for (int64_t s = 0; s < nsteps; ++s)
+    FUSCHK(FUS_TH_CALL(th, thermal_step, th, dt, heat_scale));
+  HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  return FUS_OK;
 }
 
 int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nsteps)

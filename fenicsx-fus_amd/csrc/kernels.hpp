@@ -3620,6 +3620,142 @@ k_monitor_finalise(int64_t n, const double* __restrict__ plane, double num, doub
   }
 }
 
+// ---- Pennes bioheat model (fus_thermal_*, fusmi.h) -------------------------------------------------------------------
+// State: the temperature rise theta over the baseline, rho C dtheta/dt = div(k grad theta) - W theta + Q, discretised as
+//   dtheta/dt = f(theta) = (K(-k) theta - m_W .* theta + sigma h) ./ m_C
+// with the diagonal vectors m_C = M(rho C) 1, m_W = M(W) 1 and the heat load h (W per DOF).  One launch per RK4 stage
+// after the operator's two (k_block_op, k_shared_reduce) finishes the stage: with b = K(-k) Theta_i for the stage input
+// Theta_i (Theta_0 = theta_0),
+//   k_i = (b - m_W Theta_i + sigma h) / m_C
+//   STAGE 0 (first):   acc = theta_0 + dt b_0 k_0,   Theta_1 = theta_0 + dt a_1 k_0      (theta_0 is the stage input)
+//   STAGE 1 (middle):  acc += dt b_i k_i,            Theta_{i+1} = theta_0 + dt a_{i+1} k_i   (in place over Theta_i)
+//   STAGE 3 (last):    theta_0 = acc + dt b_3 k_3,   D += (dt / 60) exp2(-c (43 - T)),  T = t_base + theta_0 in double,
+//                      c = 1 for T >= 43, else 2 (CEM43, rectangle rule on the end-of-step temperature)
+// A streaming kernel in the monitor kernel's form: a thread takes 16 bytes of every vector (2 doubles / 4 floats), all
+// accesses 16-byte and non-temporal, a grid-stride loop, no LDS, no atomics.  All vectors are n_internal long (a multiple
+// of 16) in internal numbering; their padding slots hold zeros and stay zero, since minv = 1 / m_C is 0 there.  The dose
+// plane is double for every T and is read and written once per step, in the last stage's pass.
+template <typename T>
+struct ThermalStage
+{
+  const T* b;       // K(-k) Theta_i
+  const T* th_in;   // stage input Theta_i (stage 0: theta_0)
+  T* th_out;        // next stage input (stages 0-2; may alias th_in) | new theta_0 (last stage)
+  const T* th0;     // theta_0 (middle stages)
+  T* acc;           // accumulator (written by stage 0, read and written by the middle stages, read by the last)
+  const T* minv;    // 1 / m_C, 0 in the padding slots
+  const T* mw;      // m_W
+  const T* h;       // heat load
+  double* dose;     // CEM43 plane, minutes (last stage)
+  T adt, bdt, sigma;
+  double dt60, t_base;
+};
+
+// D + (dt / 60) 2^(-c (43 - T)), every operation rounded by itself (no contraction): numpy reproduces the argument of
+// exp2 bit for bit and the sum up to the rounding of exp2
+__device__ __forceinline__ double thermal_dose_add(double D, double theta, double t_base, double dt60)
+{
+#pragma clang fp contract(off)
+  const double Tc = t_base + theta;
+  const double c = Tc >= 43.0 ? 1.0 : 2.0;
+  const double term = dt60 * exp2(-(c * (43.0 - Tc)));
+  return D + term;
+}
+
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256) k_thermal_stage(int64_t nvec, const ThermalStage<T> A)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV b = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.b) + i);
+    const TV th = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.th_in) + i);
+    const TV mi = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.minv) + i);
+    const TV mw = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.mw) + i);
+    const TV h = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.h) + i);
+    const TV k = (b - mw * th + A.sigma * h) * mi;
+    if (STAGE == 0)
+    {
+      __builtin_nontemporal_store(th + A.bdt * k, reinterpret_cast<TV*>(A.acc) + i);
+      __builtin_nontemporal_store(th + A.adt * k, reinterpret_cast<TV*>(A.th_out) + i);
+    }
+    else if (STAGE == 1)
+    {
+      const TV t0 = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.th0) + i);
+      const TV a = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.acc) + i);
+      __builtin_nontemporal_store(a + A.bdt * k, reinterpret_cast<TV*>(A.acc) + i);
+      __builtin_nontemporal_store(t0 + A.adt * k, reinterpret_cast<TV*>(A.th_out) + i);
+    }
+    else
+    {
+      const TV a = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.acc) + i);
+      const TV tn = a + A.bdt * k;
+      __builtin_nontemporal_store(tn, reinterpret_cast<TV*>(A.th_out) + i);
+#pragma unroll
+      for (int j = 0; j < VEC / 2; ++j)
+      {
+        D2* p = reinterpret_cast<D2*>(A.dose + i * VEC + 2 * j);
+        D2 d = __builtin_nontemporal_load(p);
+        d[0] = thermal_dose_add(d[0], (double)tn[2 * j], A.t_base, A.dt60);
+        d[1] = thermal_dose_add(d[1], (double)tn[2 * j + 1], A.t_base, A.dt60);
+        __builtin_nontemporal_store(d, p);
+      }
+    }
+  }
+}
+
+// Heat load h = m_q .* q with m_q = M(q_coef) 1, rounded to T once.  q != nullptr: a nodal field in internal numbering.
+// Otherwise q = Q / nsamp in double from the field monitor's sum-of-squares plane Q (k_monitor_accumulate, acc plane 1):
+// the squared RMS pressure, which never leaves the device and never passes through a square root.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_thermal_heat(int64_t nvec, const T* __restrict__ mq, const T* __restrict__ q, const double* __restrict__ Q, double nsamp,
+               T* __restrict__ h)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV m = __builtin_nontemporal_load(reinterpret_cast<const TV*>(mq) + i);
+    TV out;
+    if (q)
+      out = m * __builtin_nontemporal_load(reinterpret_cast<const TV*>(q) + i);
+    else
+    {
+#pragma unroll
+      for (int j = 0; j < VEC / 2; ++j)
+      {
+        const D2 s = __builtin_nontemporal_load(reinterpret_cast<const D2*>(Q + i * VEC + 2 * j));
+        out[2 * j] = (T)((double)m[2 * j] * (s[0] / nsamp));
+        out[2 * j + 1] = (T)((double)m[2 * j + 1] * (s[1] / nsamp));
+      }
+    }
+    __builtin_nontemporal_store(out, reinterpret_cast<TV*>(h) + i);
+  }
+}
+
+// q_coef = 2 alpha / (rho c) per cell, internal cell order (alpha: amplitude absorption, Np/m)
+template <typename T>
+__global__ void k_thermal_qcoef(int64_t n, const T* __restrict__ alpha, const T* __restrict__ rho, const T* __restrict__ c,
+                                T* __restrict__ out)
+{
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n)
+    out[e] = T(2) * alpha[e] / (rho[e] * c[e]);
+}
+
+// Power iteration of fus_thermal_lambda_max: y = (K(k) x + m_W x) / m_C from b = K(-k) x
+template <typename T>
+__global__ void k_thermal_power(int64_t n, const T* __restrict__ b, const T* __restrict__ x, const T* __restrict__ mw,
+                                const T* __restrict__ minv, T* __restrict__ y)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    y[i] = (mw[i] * x[i] - b[i]) * minv[i];
+}
+
 // halo helpers
 // pack: sendbuf[k] = vec[idx[k]] over the concatenated neighbour lists
 // Receiver sampling (the reference evaluates its solution at points with Function::eval after locating their cells:

@@ -15,6 +15,7 @@ FUS_HOST, FUS_DEVICE = 0, 1
 FUS_LINEAR, FUS_LOSSY, FUS_WESTERVELT = 0, 1, 2
 FUS_U, FUS_V = 0, 1
 FUS_MON_MAX, FUS_MON_MIN, FUS_MON_MEAN, FUS_MON_RMS, FUS_MON_COS, FUS_MON_SIN = range(6)
+FUS_TH_RISE, FUS_TH_DOSE, FUS_TH_HEAT = 0, 1, 2
 
 # every symbol include/fusmi.h declares
 SYMBOLS = [
@@ -30,6 +31,8 @@ SYMBOLS = [
     "fus_model_set_receivers", "fus_model_sample", "fus_model_record", "fus_model_get_records",
     "fus_model_monitor", "fus_model_monitor_get", "fus_model_monitor_info",
     "fus_model_set_source",
+    "fus_thermal_create", "fus_thermal_destroy", "fus_thermal_init", "fus_thermal_set", "fus_thermal_get",
+    "fus_thermal_set_heat", "fus_thermal_set_heat_from_monitor", "fus_thermal_lambda_max", "fus_thermal_steps",
 ]
 
 

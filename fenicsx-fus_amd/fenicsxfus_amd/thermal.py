@@ -1,0 +1,162 @@
+"""Pennes bioheat model and CEM43 thermal dose on the mesh of the wave models (fusmi.h "bioheat").
+
+``BioheatSpectralExplicit`` advances the temperature rise ``theta = T - t_base`` of
+
+    rho C dtheta/dt = div(k grad theta) - W theta + Q        (insulating boundaries)
+
+with classical RK4 on the GPU and accumulates the thermal dose in cumulative equivalent minutes at 43 degrees C.  The
+heat load comes from a nodal field (:meth:`set_heat`) or, without leaving the device, from the field monitor of a wave
+model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``.  The reference package
+has no thermal model; this module replaces nothing there."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import Context, check, lib, ptr
+from .mesh import Function, FunctionSpace
+from .operators import SpectralOperatorData, _array
+
+
+def cem43(temps, dt: float, t_base: float = 0.0):
+    """The dose rule in numpy: ``temps`` holds the end-of-step values of a sequence of steps of size ``dt`` seconds,
+    first axis = step -- temperatures in degrees C, or rises over ``t_base``.  Returns the cumulative equivalent
+    minutes at 43 degrees C, ``sum (dt / 60) 2^(-c (43 - T))`` with c = 1 for T >= 43 and 2 below (Sapareto and
+    Dewey), evaluated in double in the order the kernel uses."""
+    temps = np.asarray(temps, dtype=np.float64)
+    D = np.zeros(temps.shape[1:], dtype=np.float64)
+    for x in temps:
+        T = t_base + x
+        c = np.where(T >= 43.0, 1.0, 2.0)
+        D = D + (dt / 60.0) * np.exp2(-(c * (43.0 - T)))
+    return D
+
+
+class BioheatSpectralExplicit:
+    """``BioheatSpectralExplicit(mesh, k, conductivity, rho_c, perfusion=None, t_base=37.0)``: ``k`` the polynomial
+    degree; ``conductivity`` (W/m/K, >= 0), ``rho_c`` (J/m^3/K, > 0) and ``perfusion`` (w_b rho_b C_b, W/m^3/K, >= 0;
+    None = 0) one value per cell; ``t_base`` the arterial and initial temperature in degrees C.  ``model=`` shares the
+    operator data of a wave model (required for :meth:`set_heat_from`), ``data=`` an existing
+    :class:`SpectralOperatorData` (as the operator classes take it); the object then does not own the data and
+    :meth:`close` leaves it alone.  Several ranks are not supported."""
+
+    def __init__(self, mesh, k, conductivity, rho_c, perfusion=None, t_base: float = 37.0, V=None,
+                 ctx: Context | None = None, model=None, data: SpectralOperatorData | None = None):
+        self.mesh, self.t_base = mesh, float(t_base)
+        if model is not None and data is not None and data is not model.data:
+            raise _abi.FusError("BioheatSpectralExplicit: data must be the operator data of model")
+        if model is not None:
+            data = model.data
+        if data is not None:
+            self.data, self._own_data = data, False
+            self.V = data.V
+            if V is not None and V is not data.V:
+                raise _abi.FusError("BioheatSpectralExplicit: V must be the function space of the shared operator data")
+            if ctx is not None and ctx is not data.ctx:
+                raise _abi.FusError("BioheatSpectralExplicit: ctx must be the context of the shared operator data")
+        else:
+            self.V = V or FunctionSpace(mesh, k)
+            self.data, self._own_data = SpectralOperatorData(self.V, ctx), True
+        self.ctx = self.data.ctx
+        self.dtype = self.data.dtype
+        ka, ca = self._cells(conductivity, "conductivity"), self._cells(rho_c, "rho_c")
+        wa = None if perfusion is None else self._cells(perfusion, "perfusion")
+        self.h = C.c_void_p()
+        try:
+            check(lib().fus_thermal_create(self.ctx.h, self.data.h, ptr(ka), ptr(ca), ptr(wa), C.c_double(self.t_base),
+                                           C.byref(self.h)))
+        except _abi.FusError:
+            if self._own_data:
+                self.data.close()
+            raise
+
+    def _cells(self, a, name):
+        """One value per cell (a scalar is broadcast), in the operator's scalar type."""
+        a = np.asarray(_array(a), dtype=self.dtype)
+        if a.ndim and a.shape != (self.data.ncells,):
+            raise _abi.FusError(f"{name}: expected {self.data.ncells} values, one per cell, got shape {a.shape}")
+        return np.ascontiguousarray(np.broadcast_to(a, (self.data.ncells,)))
+
+    def _dofs(self, a, name, dtype=None):
+        a = np.ascontiguousarray(_array(a), dtype=dtype or self.dtype)
+        if a.shape != (self.data.ndofs,):
+            raise _abi.FusError(f"{name}: expected {self.data.ndofs} values, one per DOF, got shape {a.shape}")
+        return a
+
+    def init(self):
+        """Rise and dose to zero."""
+        check(lib().fus_thermal_init(self.h))
+
+    def set_state(self, rise=None, dose=None):
+        """Set the temperature rise (K over ``t_base``) and / or the dose (minutes, float64), one value per DOF."""
+        if rise is not None:
+            a = self._dofs(rise, "rise")
+            check(lib().fus_thermal_set(self.h, C.c_int(_abi.FUS_TH_RISE), ptr(a), C.c_int(_abi.FUS_HOST)))
+        if dose is not None:
+            a = self._dofs(dose, "dose", np.float64)
+            check(lib().fus_thermal_set(self.h, C.c_int(_abi.FUS_TH_DOSE), ptr(a), C.c_int(_abi.FUS_HOST)))
+
+    def set_heat(self, q, coef=None):
+        """Heat load ``h = (M(coef) 1) .* q``: ``q`` a nodal field (W/m^3 with ``coef`` None = 1), ``coef`` a per-cell
+        factor.  ``q`` None: no heat."""
+        if q is None:
+            check(lib().fus_thermal_set_heat(self.h, None, None, C.c_int(_abi.FUS_HOST)))
+            return
+        qa = self._dofs(q, "q")
+        ca = None if coef is None else self._cells(coef, "coef")
+        check(lib().fus_thermal_set_heat(self.h, ptr(qa), ptr(ca), C.c_int(_abi.FUS_HOST)))
+
+    def set_heat_from(self, model, absorption):
+        """Acoustic heating ``Q = 2 alpha p_rms^2 / (rho c)`` from the field monitor of ``model`` (watching u, at least
+        one sample), on the device: ``absorption`` = alpha, amplitude absorption in Np/m at the source frequency, one
+        value per cell (or a scalar).  ``model`` must be the one this object was created with (``model=``)."""
+        a = self._cells(absorption, "absorption")
+        check(lib().fus_thermal_set_heat_from_monitor(self.h, model.h, ptr(a)))
+
+    def lambda_max(self, iters: int = 20) -> float:
+        """Rayleigh quotient after ``iters`` power iterations: a lower bound of the largest eigenvalue of
+        ``m_C^-1 (K(k) + diag m_W)`` (1/s)."""
+        out = C.c_double()
+        check(lib().fus_thermal_lambda_max(self.h, C.c_int(iters), C.byref(out)))
+        return out.value
+
+    def stable_dt(self) -> float:
+        """``2 / lambda_max(20)``: inside the RK4 limit 2.785 / lambda_max while the quotient has reached 0.72 of it."""
+        return 2.0 / self.lambda_max(20)
+
+    def steps(self, dt: float, n: int, heat_scale: float = 1.0):
+        """``n`` RK4 steps of ``dt`` seconds with the heat load scaled by ``heat_scale`` (duty cycle; 0 = cooling)."""
+        check(lib().fus_thermal_steps(self.h, C.c_double(dt), C.c_int64(n), C.c_double(heat_scale)))
+
+    def _get(self, which, dtype) -> Function:
+        f = Function(self.V, dtype)
+        check(lib().fus_thermal_get(self.h, C.c_int(which), ptr(f.x.array), C.c_int(_abi.FUS_HOST)))
+        return f
+
+    def rise(self) -> Function:
+        """Temperature rise over ``t_base`` (K)."""
+        return self._get(_abi.FUS_TH_RISE, self.dtype)
+
+    def temperature(self) -> Function:
+        """``t_base + rise`` in degrees C."""
+        f = self.rise()
+        f.x.array[:] = f.x.array + f.x.array.dtype.type(self.t_base)
+        return f
+
+    def dose(self) -> Function:
+        """CEM43 in minutes (float64)."""
+        return self._get(_abi.FUS_TH_DOSE, np.float64)
+
+    def heat(self) -> Function:
+        """The heat load vector ``h`` (W per DOF)."""
+        return self._get(_abi.FUS_TH_HEAT, self.dtype)
+
+    def close(self):
+        """Frees the thermal object, and the operator data if this object created it."""
+        if self.h:
+            lib().fus_thermal_destroy(self.h)
+            self.h = C.c_void_p()
+        if self._own_data:
+            self.data.close()

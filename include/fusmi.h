@@ -349,6 +349,64 @@ int fus_model_monitor_info(fus_model* model, int64_t* nsamples, double* t_first,
  * every sharer of a DOF passes the same values for it (they are functions of position). */
 int fus_model_set_source(fus_model* model, const void* amplitude, const void* delay, double duration, int space);
 
+/* ---- bioheat: Pennes equation and CEM43 thermal dose on the operator's mesh ---------------------------------------
+ * What a focused-ultrasound user computes from the pressure maps: the temperature rise the beam causes and the thermal
+ * dose it leaves.  (The reference has no thermal model; this section replaces nothing there.)
+ *
+ * State: the temperature RISE theta = T - t_base over a uniform baseline t_base (arterial and initial temperature,
+ * degrees C); the rise and not the temperature, so that FUS_F32 objects do not lose a 0.01 K increment against 37.
+ *   rho C dtheta/dt = div(k grad theta) - W theta + Q,     natural (insulating) boundaries
+ * Per-cell coefficients, host T[ncells] in caller cell numbering: conductivity k >= 0 (W/m/K), rho_c > 0 (J/m^3/K),
+ * perfusion W = w_b rho_b C_b >= 0 (W/m^3/K; NULL = 0).  On the GLL-collocated space of the wave models, with the
+ * library's K(c) and M(c) (u^T K(1) u = integral of |grad u|^2):
+ *   m_C = M(rho_c) 1     m_W = M(W) 1     h = (M(q_coef) 1) .* q                  (all diagonal)
+ *   dtheta/dt = f(theta) = ( K(-k) theta - m_W .* theta + sigma h ) ./ m_C
+ * q is a nodal field, q_coef a per-cell factor (NULL = 1), h the heat load in W per DOF, sigma the scalar heat_scale of a
+ * fus_thermal_steps call (duty cycle; 0 = cooling).  Acoustic heating Q = 2 alpha p_rms^2 / (rho c): q = p_rms^2,
+ * q_coef = 2 alpha / (rho c), alpha the amplitude absorption in Np/m at the source frequency.
+ * Time stepping: classical RK4, a = (0, 1/2, 1/2, 1), b = (1/6, 1/3, 1/3, 1/6); f has no explicit time dependence.
+ * Per stage the operator's two launches and one streaming kernel (profile name "thermal").
+ * Dose: double[ndofs] for both scalar types.  After each completed step of size dt that ends in theta_n, in double:
+ *   T = t_base + theta_n;   c = 1 if T >= 43 else 2;   D += (dt / 60) * exp2(-c * (43 - T))
+ * -- CEM43 in minutes after Sapareto and Dewey, a rectangle rule on the end-of-step temperature, added in the last
+ * stage's pass (the dose plane is read and written once per step).
+ * Stable step: RK4 needs dt <= 2.785 / lambda_max of m_C^-1 (K(k) + diag m_W).  fus_thermal_lambda_max runs a power
+ * iteration from x_d = 1 + 0.5 sin(37 d + 1) (d = caller DOF number): iters times y = (K(k) x + m_W .* x) ./ m_C,
+ * rho = (x . (m_C .* y)) / (x . (m_C .* x)), x = y / sqrt(y . (m_C .* y)); it returns the last rho, which never exceeds
+ * lambda_max (20 iterations reach about 0.97 of it on small meshes; dt = 2 / rho_20 stays inside the limit while
+ * rho_20 >= 0.72 lambda_max).  Setup-time work: the dot products are taken on the host from the pulled vector.
+ *
+ *   fus_thermal_create   on an existing operator object, also one created with "fields" = 2; several thermal objects and wave
+ *                        models may share one op and run in turns on the context's stream
+ *   fus_thermal_init     theta = 0, D = 0
+ *   fus_thermal_set      which = FUS_TH_RISE: T[ndofs]; FUS_TH_DOSE: double[ndofs]; caller numbering, `space`
+ *   fus_thermal_get      FUS_TH_RISE, FUS_TH_HEAT (= h): T[ndofs]; FUS_TH_DOSE: double[ndofs]
+ *   fus_thermal_set_heat q: T[ndofs], q_coef: T[ncells] or NULL (= 1), both in `space`; q == NULL: h = 0
+ *   fus_thermal_set_heat_from_monitor   h from the field monitor of a wave model on the SAME fus_op, without leaving
+ *                        the device: q = Q / n from the monitor's sum-of-squares plane and sample count, formed in
+ *                        double (the RMS map is never rounded through a square root), q_coef = 2 alpha / (rho c) with
+ *                        the model's rho0 and c0; absorption = alpha, host T[ncells], >= 0.  The monitor keeps sampling
+ *   fus_thermal_steps    nsteps RK4 steps of size dt with heat_scale sigma
+ * Errors; argument and call-sequence errors (FUS_ERR_ARG, FUS_ERR_STATE) are found before anything is enqueued and leave the
+ * state and the heat load as they were.  A FUS_ERR_HIP inside fus_thermal_steps returns at the failing step: the steps before
+ * it have been applied and the stream is not synchronised.  FUS_ERR_ARG: null arguments; rho_c <= 0, a negative or
+ * non-finite k, W or alpha; dt <= 0; iters < 1; a fus_model on another fus_op than the thermal object's.  FUS_ERR_STATE:
+ * steps before fus_thermal_init / fus_thermal_set; fus_thermal_set_heat_from_monitor while the model's monitor is off,
+ * has no sample, or watches FUS_V; an op on which fus_op_set_neighbours was called -- SEVERAL RANKS ARE OUT OF SCOPE:
+ * the operator action inside a thermal step does no inter-rank reduction. */
+typedef struct fus_thermal fus_thermal;
+enum { FUS_TH_RISE = 0, FUS_TH_DOSE = 1, FUS_TH_HEAT = 2 };
+int fus_thermal_create(fus_ctx* ctx, fus_op* op, const void* conductivity, const void* rho_c,
+                       const void* perfusion /* NULL = 0 */, double t_base, fus_thermal** thermal);
+int fus_thermal_destroy(fus_thermal* thermal);
+int fus_thermal_init(fus_thermal* thermal);
+int fus_thermal_set(fus_thermal* thermal, int which, const void* in, int space);
+int fus_thermal_get(fus_thermal* thermal, int which, void* out, int space);
+int fus_thermal_set_heat(fus_thermal* thermal, const void* q, const void* q_coef, int space);
+int fus_thermal_set_heat_from_monitor(fus_thermal* thermal, fus_model* model, const void* absorption /* T[ncells], Np/m */);
+int fus_thermal_lambda_max(fus_thermal* thermal, int iters, double* lambda);
+int fus_thermal_steps(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale);
+
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
 
@@ -379,7 +437,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the library's own kernels on the stream they run on.  Names:
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
- * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform).  total_ms/count accumulate since the last enable.
+ * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform),
+ * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared").  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

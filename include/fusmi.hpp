@@ -13,6 +13,7 @@
 //     init(); rk4(t0, tf, dt); u_sol(); number_of_dofs()    init(); rk4(t0, tf, dt); u_sol(); number_of_dofs()
 //     Linear.hpp:52-347
 //   LossySpectral3D (Lossy.hpp:56-342), WesterveltSpectral3D (Westervelt.hpp:58-373): + delta0 (, beta0)
+//   (none: the reference has no thermal model)          BioheatSpectral3D<T,P>(data, conductivity, rho_c, perfusion)
 //
 // Where the reference takes a dolfinx::fem::FunctionSpace / Mesh / MeshTags and derives arrays from
 // them (spectral_op.hpp:135-171, Linear.hpp:113-118), these classes take those arrays directly
@@ -357,6 +358,65 @@ public:
   {
   }
 };
+
+// Pennes bioheat model and CEM43 dose on the operator's mesh (fusmi.h "bioheat"; the reference has no thermal model):
+//   rho C dtheta/dt = div(k grad theta) - W theta + Q for the temperature RISE theta over t_base, classical RK4.
+// conductivity, rho_c, perfusion (nullptr = 0): one value per cell.  One rank only.
+template <typename T, int P>
+class BioheatSpectral3D
+{
+public:
+  BioheatSpectral3D(std::shared_ptr<SpectralOperatorData<T, P>> data, const T* conductivity, const T* rho_c,
+                    const T* perfusion = nullptr, double t_base = 37.0)
+      : d_(std::move(data))
+  {
+    check(fus_thermal_create(d_->context()->handle(), d_->handle(), conductivity, rho_c, perfusion, t_base, &h_));
+  }
+  ~BioheatSpectral3D() { fus_thermal_destroy(h_); }
+  BioheatSpectral3D(const BioheatSpectral3D&) = delete;
+  BioheatSpectral3D& operator=(const BioheatSpectral3D&) = delete;
+  void init() { check(fus_thermal_init(h_)); }  // rise = 0, dose = 0
+  void set_state(const T* rise, const double* dose = nullptr)
+  {
+    if (rise)
+      check(fus_thermal_set(h_, FUS_TH_RISE, rise, FUS_HOST));
+    if (dose)
+      check(fus_thermal_set(h_, FUS_TH_DOSE, dose, FUS_HOST));
+  }
+  // h = (M(q_coef) 1) .* q: q [ndofs], q_coef [ncells] or nullptr (= 1); q == nullptr: no heat
+  void set_heat(const T* q, const T* q_coef = nullptr) { check(fus_thermal_set_heat(h_, q, q_coef, FUS_HOST)); }
+  // acoustic heating 2 alpha p_rms^2 / (rho c) from the field monitor of a wave model on the same operator data
+  template <typename Model>
+  void set_heat_from(const Model& model, const T* absorption)
+  {
+    check(fus_thermal_set_heat_from_monitor(h_, model.handle(), absorption));
+  }
+  double lambda_max(int iters = 20) const
+  {
+    double l = 0;
+    check(fus_thermal_lambda_max(h_, iters, &l));
+    return l;
+  }
+  double stable_dt() const { return 2.0 / lambda_max(20); }
+  void steps(double dt, std::int64_t nsteps, double heat_scale = 1.0) { check(fus_thermal_steps(h_, dt, nsteps, heat_scale)); }
+  std::vector<T> rise() const { return get<T>(FUS_TH_RISE); }
+  std::vector<T> heat() const { return get<T>(FUS_TH_HEAT); }
+  std::vector<double> dose() const { return get<double>(FUS_TH_DOSE); }  // CEM43, minutes
+  fus_thermal* handle() const { return h_; }
+
+private:
+  template <typename U>
+  std::vector<U> get(int which) const
+  {
+    std::vector<U> out((size_t)d_->ndofs());
+    check(fus_thermal_get(h_, which, out.data(), FUS_HOST));
+    return out;
+  }
+  std::shared_ptr<SpectralOperatorData<T, P>> d_;
+  fus_thermal* h_ = nullptr;
+};
+template <typename T, int P>
+using BioheatSpectral2D = BioheatSpectral3D<T, P>;  // SpaceView::tdim = 2
 
 // delta = 2 alpha c0^3 / w0^2, alpha in Np/m (Lossy.hpp:375-379)
 template <typename T>
