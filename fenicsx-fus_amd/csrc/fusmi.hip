@@ -25,6 +25,7 @@
 
 #include "kernels.hpp"
 #include "layout.hpp"
+#include "sts_coef.hpp"
 #include "tables.hpp"
 
 using namespace fus;
@@ -2084,6 +2085,7 @@ struct fus_thermal
   // n_internal vectors of T: rise theta_0, stage input, accumulator, operator result, 1 / m_C, m_C, m_W, heat load h
   void *th0 = nullptr, *ths = nullptr, *acc = nullptr, *b = nullptr, *minv = nullptr, *mc = nullptr, *mw = nullptr,
        *h = nullptr;
+  void *f0 = nullptr;          // F_0 of the super-time-stepping scheme: allocated by the first fus_thermal_steps_sts call
   void *kneg = nullptr;        // -k per cell, internal cell order
   double* dose = nullptr;      // CEM43 minutes, n_internal doubles
   double* d_stage = nullptr;   // ndofs doubles in caller numbering (dose in / out)
@@ -2199,6 +2201,43 @@ static int thermal_step(fus_thermal* th, double dt_, double sigma)
       hipLaunchKernelGGL((k_thermal_stage<T, 1>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
     else
       hipLaunchKernelGGL((k_thermal_stage<T, 3>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    HIPCHK(hipGetLastError());
+  }
+  return FUS_OK;
+}
+
+// one RKL2 step of c.s stages (sts_coef.hpp): per stage the operator's two launches and k_thermal_sts_stage.  Y_0 stays in
+// th0 until the last stage overwrites it, F_0 sits in f0, and Y_1, Y_2, ... alternate between ths and acc: Y_j lands
+// where Y_{j-2} was, except Y_2, whose Y_{j-2} is Y_0
+template <typename T>
+static int thermal_step_sts(fus_thermal* th, double dt_, double sigma, const fus::StsCoef& c)
+{
+  fus_op* op = th->op;
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec);
+  T* rot[2] = {static_cast<T*>(th->ths), static_cast<T*>(th->acc)};
+  T* th0 = static_cast<T*>(th->th0);
+  for (int j = 1; j <= c.s; ++j)
+  {
+    const T* y1 = j == 1 ? th0 : rot[(j - 2) & 1];
+    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, y1, th->b));
+    ThermalSts<T> A;
+    A.b = static_cast<const T*>(th->b), A.y1 = y1;
+    A.y2 = j <= 2 ? th0 : rot[(j - 1) & 1];
+    A.y0 = th0, A.f0 = static_cast<T*>(th->f0);
+    A.out = j == c.s ? th0 : rot[(j - 1) & 1];
+    A.minv = static_cast<const T*>(th->minv), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+    A.dose = th->dose;
+    A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
+    A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
+    A.dt120 = dt_ / 120.0, A.t_base = th->t_base;
+    ProfScope ps(th->ctx, "thermal_sts");
+    if (j == 1)
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 0>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    else if (j < c.s)
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 1>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    else
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 2>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
     HIPCHK(hipGetLastError());
   }
   return FUS_OK;
@@ -3742,6 +3781,45 @@ int fus_thermal_steps(fus_thermal* th, double dt, int64_t nsteps, double heat_sc
   for (int64_t s = 0; s < nsteps; ++s)
     FUSCHK(FUS_TH_CALL(th, thermal_step, th, dt, heat_scale));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_thermal_steps_sts(fus_thermal* th, double dt, int64_t nsteps, double heat_scale, int stages)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: null argument");
+  fus::StsCoef coef;
+  if (!fus::sts_coefficients(stages, &coef))
+    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: stages must lie in 2..32");
+  if (!(dt > 0) || !std::isfinite(dt))
+    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: dt must be positive and finite");
+  if (nsteps < 0 || !std::isfinite(heat_scale))
+    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: nsteps must be >= 0 and heat_scale finite");
+  if (!th->initialised)
+    return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called before fus_thermal_steps_sts");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  if (!th->f0)   // objects that never use the scheme keep their footprint
+    FUSCHK(dalloc_bytes(th->allocs, &th->f0, th->op->L.n_internal * th->op->ts, true, th->ctx->stream));
+  for (int64_t s = 0; s < nsteps; ++s)
+    FUSCHK(FUS_TH_CALL(th, thermal_step_sts, th, dt, heat_scale, coef));
+  HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_thermal_stable_dt(fus_thermal* th, int iters, int stages, double* dt)
+{
+  if (!th || !dt)
+    return fail(FUS_ERR_ARG, "fus_thermal_stable_dt: null argument");
+  if (iters < 1)
+    return fail(FUS_ERR_ARG, "fus_thermal_stable_dt: iters must be at least 1");
+  if (stages != 0 && !fus::sts_stages_ok(stages))
+    return fail(FUS_ERR_ARG, "fus_thermal_stable_dt: stages must be 0 (RK4) or lie in 2..32");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  double rho = 0.0;
+  FUSCHK(FUS_TH_CALL(th, thermal_lambda_max, th, iters, &rho));
+  if (!(rho > 0.0))
+    return fail(FUS_ERR_STATE, "fus_thermal_stable_dt: the operator is zero (k = 0 and W = 0 everywhere): any step is stable");
+  *dt = stages == 0 ? 2.0 / rho : 0.72 * fus::sts_beta(stages) / rho;
   return FUS_OK;
 }
 

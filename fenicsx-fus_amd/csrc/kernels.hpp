@@ -3706,6 +3706,89 @@ __global__ void __launch_bounds__(256) k_thermal_stage(int64_t nvec, const Therm
   }
 }
 
+// ---- super-time-stepping of the bioheat model (fus_thermal_steps_sts; coefficients: sts_coef.hpp) ----
+// One launch per RKL2 stage after the operator's two finishes the stage: with b = K(-k) Y_{j-1},
+//   f = (b - m_W Y_{j-1} + sigma h) / m_C
+//   KIND 0 (first):   F_0 = f,  Y_1 = Y_0 + mdt f                                    (y1 = Y_0; out = Y_1)
+//   KIND 1 (middle):  Y_j = mu Y_{j-1} + nu Y_{j-2} + om Y_0 + mdt f + gdt F_0       (out = the place of Y_{j-2}, or a
+//                     buffer of its own for j = 2, where Y_{j-2} = Y_0 is kept)
+//   KIND 2 (last):    theta = Y_s over Y_0 (same index, same thread; with s = 2 also y2 = Y_0), and the dose by the
+//                     trapezoid rule on the temperatures at both ends of the step, in double:
+//                     D += (dt / 120) (R(T_old) + R(T_new)),  R(T) = exp2(-c (43 - T)),  T = t_base + theta
+// with om = 1 - mu - nu, mdt = mut_j dt, gdt = gat_j dt rounded to T on the host.  The form of k_thermal_stage: 16-byte
+// non-temporal accesses, a grid-stride loop, no LDS, no atomics; n_internal-long vectors whose padding stays zero
+// (minv = 0 there).  out may alias y2 and y0: every load of an index precedes its store in the one thread that owns it.
+template <typename T>
+struct ThermalSts
+{
+  const T* b;       // K(-k) Y_{j-1}
+  const T* y1;      // Y_{j-1}
+  const T* y2;      // Y_{j-2} (middle, last)
+  const T* y0;      // Y_0 (middle, last)
+  T* f0;            // F_0: written by the first stage, read by the others
+  T* out;           // Y_j
+  const T* minv;    // 1 / m_C, 0 in the padding slots
+  const T* mw;      // m_W
+  const T* h;       // heat load
+  double* dose;     // CEM43 plane, minutes (last stage)
+  T mu, nu, om, mdt, gdt, sigma;
+  double dt120, t_base;
+};
+
+// D + (dt / 120) (R(T_old) + R(T_new)), every operation rounded by itself as in thermal_dose_add
+__device__ __forceinline__ double thermal_dose_add_trapezoid(double D, double th_old, double th_new, double t_base,
+                                                             double dt120)
+{
+#pragma clang fp contract(off)
+  const double To = t_base + th_old, Tn = t_base + th_new;
+  const double co = To >= 43.0 ? 1.0 : 2.0, cn = Tn >= 43.0 ? 1.0 : 2.0;
+  const double ro = exp2(-(co * (43.0 - To))), rn = exp2(-(cn * (43.0 - Tn)));
+  const double term = dt120 * (ro + rn);
+  return D + term;
+}
+
+template <typename T, int KIND>
+__global__ void __launch_bounds__(256) k_thermal_sts_stage(int64_t nvec, const ThermalSts<T> A)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV b = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.b) + i);
+    const TV y1 = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.y1) + i);
+    const TV mi = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.minv) + i);
+    const TV mw = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.mw) + i);
+    const TV h = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.h) + i);
+    const TV f = (b - mw * y1 + A.sigma * h) * mi;
+    if (KIND == 0)
+    {
+      __builtin_nontemporal_store(f, reinterpret_cast<TV*>(A.f0) + i);
+      __builtin_nontemporal_store(y1 + A.mdt * f, reinterpret_cast<TV*>(A.out) + i);
+    }
+    else
+    {
+      const TV y2 = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.y2) + i);
+      const TV y0 = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.y0) + i);
+      const TV f0 = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.f0) + i);
+      const TV yn = A.mu * y1 + A.nu * y2 + A.om * y0 + A.mdt * f + A.gdt * f0;
+      __builtin_nontemporal_store(yn, reinterpret_cast<TV*>(A.out) + i);
+      if (KIND == 2)
+      {
+#pragma unroll
+        for (int j = 0; j < VEC / 2; ++j)
+        {
+          D2* p = reinterpret_cast<D2*>(A.dose + i * VEC + 2 * j);
+          D2 d = __builtin_nontemporal_load(p);
+          d[0] = thermal_dose_add_trapezoid(d[0], (double)y0[2 * j], (double)yn[2 * j], A.t_base, A.dt120);
+          d[1] = thermal_dose_add_trapezoid(d[1], (double)y0[2 * j + 1], (double)yn[2 * j + 1], A.t_base, A.dt120);
+          __builtin_nontemporal_store(d, p);
+        }
+      }
+    }
+  }
+}
+
 // Heat load h = m_q .* q with m_q = M(q_coef) 1, rounded to T once.  q != nullptr: a nodal field in internal numbering.
 // Otherwise q = Q / nsamp in double from the field monitor's sum-of-squares plane Q (k_monitor_accumulate, acc plane 1):
 // the squared RMS pressure, which never leaves the device and never passes through a square root.

@@ -4,7 +4,9 @@
 
     rho C dtheta/dt = div(k grad theta) - W theta + Q        (insulating boundaries)
 
-with classical RK4 on the GPU and accumulates the thermal dose in cumulative equivalent minutes at 43 degrees C.  The
+with classical RK4 on the GPU, or with the super-time-stepping scheme RKL2 (``steps(..., stages=s)``: s operator
+applications per step, a step about ``(s^2 + s - 2) / 5.6`` times the RK4 step), and accumulates the thermal dose in
+cumulative equivalent minutes at 43 degrees C.  The
 heat load comes from a nodal field (:meth:`set_heat`) or, without leaving the device, from the field monitor of a wave
 model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``.  The reference package
 has no thermal model; this module replaces nothing there."""
@@ -32,6 +34,39 @@ def cem43(temps, dt: float, t_base: float = 0.0):
         c = np.where(T >= 43.0, 1.0, 2.0)
         D = D + (dt / 60.0) * np.exp2(-(c * (43.0 - T)))
     return D
+
+
+STS_MIN_STAGES, STS_MAX_STAGES = 2, 32
+
+
+def rkl2_coefficients(s: int):
+    """``(mu, nu, mut, gat)`` of the s-stage Runge-Kutta-Legendre scheme of second order (Meyer, Balsara and Aslam, J.
+    Comput. Phys. 257, 2014), float64 arrays of length s + 1 indexed by the stage j = 1..s (entry 0, and mu, nu, gat
+    of stage 1, are 0); mirrors csrc/sts_coef.hpp bit for bit.  One step of y' = f(y):
+
+        Y_0 = y,  F_0 = f(Y_0),  Y_1 = Y_0 + mut_1 dt F_0
+        Y_j = mu_j Y_{j-1} + nu_j Y_{j-2} + (1 - mu_j - nu_j) Y_0 + mut_j dt f(Y_{j-1}) + gat_j dt F_0,   y <- Y_s
+
+    stable on the negative real axis for ``dt lambda <= (s^2 + s - 2) / 2``."""
+    s = int(s)
+    if not STS_MIN_STAGES <= s <= STS_MAX_STAGES:
+        raise ValueError(f"stages must lie in {STS_MIN_STAGES}..{STS_MAX_STAGES}, got {s}")
+
+    def b(j):
+        x = float(j)
+        return 1.0 / 3.0 if j < 3 else (x * x + x - 2.0) / (2.0 * x * (x + 1.0))
+
+    x = float(s)
+    w1 = 4.0 / (x * x + x - 2.0)
+    mu, nu, mut, gat = (np.zeros(s + 1) for _ in range(4))
+    mut[1] = b(1) * w1
+    for j in range(2, s + 1):
+        y = float(j)
+        mu[j] = (2.0 * y - 1.0) / y * b(j) / b(j - 1)
+        nu[j] = -((y - 1.0) / y) * b(j) / b(j - 2)
+        mut[j] = float(mu[j]) * w1
+        gat[j] = -((1.0 - b(j - 1)) * float(mut[j]))
+    return mu, nu, mut, gat
 
 
 class BioheatSpectralExplicit:
@@ -122,13 +157,25 @@ class BioheatSpectralExplicit:
         check(lib().fus_thermal_lambda_max(self.h, C.c_int(iters), C.byref(out)))
         return out.value
 
-    def stable_dt(self) -> float:
-        """``2 / lambda_max(20)``: inside the RK4 limit 2.785 / lambda_max while the quotient has reached 0.72 of it."""
-        return 2.0 / self.lambda_max(20)
+    def stable_dt(self, stages: int = 0) -> float:
+        """``stages`` = 0: ``2 / lambda_max(20)``, inside the RK4 limit 2.785 / lambda_max while the quotient has reached
+        0.72 of it.  ``stages`` = s in 2..32: ``0.72 (s^2 + s - 2) / (2 lambda_max(20))``, inside the RKL2 limit
+        (s^2 + s - 2) / (2 lambda_max) with the same margin, under the same condition."""
+        out = C.c_double()
+        check(lib().fus_thermal_stable_dt(self.h, C.c_int(20), C.c_int(stages), C.byref(out)))
+        return out.value
 
-    def steps(self, dt: float, n: int, heat_scale: float = 1.0):
-        """``n`` RK4 steps of ``dt`` seconds with the heat load scaled by ``heat_scale`` (duty cycle; 0 = cooling)."""
-        check(lib().fus_thermal_steps(self.h, C.c_double(dt), C.c_int64(n), C.c_double(heat_scale)))
+    def steps(self, dt: float, n: int, heat_scale: float = 1.0, stages: int = 0):
+        """``n`` steps of ``dt`` seconds with the heat load scaled by ``heat_scale`` (duty cycle; 0 = cooling).
+        ``stages`` = 0: classical RK4, the dose by the rectangle rule on the end-of-step temperature.  ``stages`` = s in
+        2..32: the super-time-stepping scheme RKL2 (:func:`rkl2_coefficients`) with s operator applications per step,
+        the dose by the trapezoid rule on the temperatures at both ends of the step; take ``dt`` from
+        ``stable_dt(stages=s)``.  Segments of either kind may follow each other."""
+        if stages == 0:
+            check(lib().fus_thermal_steps(self.h, C.c_double(dt), C.c_int64(n), C.c_double(heat_scale)))
+        else:
+            check(lib().fus_thermal_steps_sts(self.h, C.c_double(dt), C.c_int64(n), C.c_double(heat_scale),
+                                              C.c_int(stages)))
 
     def _get(self, which, dtype) -> Function:
         f = Function(self.V, dtype)

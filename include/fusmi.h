@@ -375,6 +375,23 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  * rho = (x . (m_C .* y)) / (x . (m_C .* x)), x = y / sqrt(y . (m_C .* y)); it returns the last rho, which never exceeds
  * lambda_max (20 iterations reach about 0.97 of it on small meshes; dt = 2 / rho_20 stays inside the limit while
  * rho_20 >= 0.72 lambda_max).  Setup-time work: the dot products are taken on the host from the pulled vector.
+ * Super-time-stepping (fus_thermal_steps_sts): the RK4 step is bound by the diffusion limit alone, which grows like
+ * P^4 / h^2 while the temperature field stays smooth.  The stabilised Runge-Kutta-Legendre scheme of second order (RKL2:
+ * Meyer, Balsara and Aslam, J. Comput. Phys. 257, 2014) takes s stages of one operator application each and is stable
+ * for dt lambda_max <= beta_s = (s^2 + s - 2) / 2; the discrete operator is symmetric negative semi-definite in the m_C
+ * inner product, so the negative real axis is all that matters.  With b_0 = b_1 = b_2 = 1/3,
+ * b_j = (j^2 + j - 2) / (2 j (j + 1)), a_j = 1 - b_j, w1 = 4 / (s^2 + s - 2), mut_1 = b_1 w1 and, for j = 2..s,
+ * mu_j = (2j - 1)/j b_j / b_{j-1}, nu_j = -(j - 1)/j b_j / b_{j-2}, mut_j = mu_j w1, gat_j = -a_{j-1} mut_j:
+ *   Y_0 = theta,  F_0 = f(Y_0),  Y_1 = Y_0 + mut_1 dt F_0
+ *   Y_j = mu_j Y_{j-1} + nu_j Y_{j-2} + (1 - mu_j - nu_j) Y_0 + mut_j dt f(Y_{j-1}) + gat_j dt F_0,    theta <- Y_s
+ * Per stage the operator's two launches and one streaming kernel (profile name "thermal_sts"); one more state-sized
+ * vector (F_0) than RK4, allocated by the first fus_thermal_steps_sts call.  stages lies in 2..32, the range over which
+ * the stability polynomial and the rounding behaviour of the recurrence have been checked.  The steps are long against
+ * the dose rate's growth, so this path integrates the dose by the TRAPEZOID rule, after each step from theta_old to
+ * theta_new, in double:   D += (dt / 120) * (R(T_old) + R(T_new)),   R(T) = exp2(-c * (43 - T)),   c = 1 if T >= 43 else 2.
+ * RK4 steps and super-steps of any stage count may follow each other on one object.
+ * fus_thermal_stable_dt: stages = 0 gives the RK4 step 2 / rho_iters; stages = s in 2..32 gives 0.72 beta_s / rho_iters,
+ * the same margin (0.72 = 2 / 2.785) and safe under the same condition, rho_iters >= 0.72 lambda_max.
  *
  *   fus_thermal_create   on an existing operator object, also one created with "fields" = 2; several thermal objects and wave
  *                        models may share one op and run in turns on the context's stream
@@ -387,11 +404,16 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  *                        double (the RMS map is never rounded through a square root), q_coef = 2 alpha / (rho c) with
  *                        the model's rho0 and c0; absorption = alpha, host T[ncells], >= 0.  The monitor keeps sampling
  *   fus_thermal_steps    nsteps RK4 steps of size dt with heat_scale sigma
+ *   fus_thermal_steps_sts   nsteps RKL2 steps of `stages` stages each; states and argument checks as fus_thermal_steps,
+ *                        and FUS_ERR_ARG for stages outside 2..32
+ *   fus_thermal_stable_dt   lambda_max(iters) turned into a step for RK4 (stages = 0) or RKL2 (stages in 2..32)
  * Errors; argument and call-sequence errors (FUS_ERR_ARG, FUS_ERR_STATE) are found before anything is enqueued and leave the
  * state and the heat load as they were.  A FUS_ERR_HIP inside fus_thermal_steps returns at the failing step: the steps before
  * it have been applied and the stream is not synchronised.  FUS_ERR_ARG: null arguments; rho_c <= 0, a negative or
- * non-finite k, W or alpha; dt <= 0; iters < 1; a fus_model on another fus_op than the thermal object's.  FUS_ERR_STATE:
- * steps before fus_thermal_init / fus_thermal_set; fus_thermal_set_heat_from_monitor while the model's monitor is off,
+ * non-finite k, W or alpha; dt <= 0; iters < 1; stages outside 2..32 (fus_thermal_stable_dt: 0 or 2..32); a fus_model on
+ * another fus_op than the thermal object's.  FUS_ERR_STATE:
+ * steps before fus_thermal_init / fus_thermal_set; fus_thermal_stable_dt on a zero operator (k = 0 and W = 0 everywhere:
+ * every step is stable); fus_thermal_set_heat_from_monitor while the model's monitor is off,
  * has no sample, or watches FUS_V; an op on which fus_op_set_neighbours was called -- SEVERAL RANKS ARE OUT OF SCOPE:
  * the operator action inside a thermal step does no inter-rank reduction. */
 typedef struct fus_thermal fus_thermal;
@@ -406,6 +428,8 @@ int fus_thermal_set_heat(fus_thermal* thermal, const void* q, const void* q_coef
 int fus_thermal_set_heat_from_monitor(fus_thermal* thermal, fus_model* model, const void* absorption /* T[ncells], Np/m */);
 int fus_thermal_lambda_max(fus_thermal* thermal, int iters, double* lambda);
 int fus_thermal_steps(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale);
+int fus_thermal_steps_sts(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale, int stages);
+int fus_thermal_stable_dt(fus_thermal* thermal, int iters, int stages, double* dt);
 
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
@@ -438,7 +462,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
  * HIP-event timing of the library's own kernels on the stream they run on.  Names:
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
  * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform),
- * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared").  total_ms/count accumulate since the last enable.
+ * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared"), "thermal_sts" (the
+ * same for a super-time-stepping stage).  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

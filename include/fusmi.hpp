@@ -360,7 +360,8 @@ public:
 };
 
 // Pennes bioheat model and CEM43 dose on the operator's mesh (fusmi.h "bioheat"; the reference has no thermal model):
-//   rho C dtheta/dt = div(k grad theta) - W theta + Q for the temperature RISE theta over t_base, classical RK4.
+//   rho C dtheta/dt = div(k grad theta) - W theta + Q for the temperature RISE theta over t_base, classical RK4 or,
+//   with stages = s in 2..32, the super-time-stepping scheme RKL2 (s operator applications per step, trapezoid dose).
 // conductivity, rho_c, perfusion (nullptr = 0): one value per cell.  One rank only.
 template <typename T, int P>
 class BioheatSpectral3D
@@ -397,8 +398,18 @@ public:
     check(fus_thermal_lambda_max(h_, iters, &l));
     return l;
   }
-  double stable_dt() const { return 2.0 / lambda_max(20); }
-  void steps(double dt, std::int64_t nsteps, double heat_scale = 1.0) { check(fus_thermal_steps(h_, dt, nsteps, heat_scale)); }
+  // stages = 0: 2 / lambda_max(20), the RK4 step; stages = s: 0.72 (s^2 + s - 2) / (2 lambda_max(20)), the RKL2 step
+  double stable_dt(int stages = 0) const
+  {
+    double dt = 0;
+    check(fus_thermal_stable_dt(h_, 20, stages, &dt));
+    return dt;
+  }
+  void steps(double dt, std::int64_t nsteps, double heat_scale = 1.0, int stages = 0)
+  {
+    check(stages == 0 ? fus_thermal_steps(h_, dt, nsteps, heat_scale)
+                      : fus_thermal_steps_sts(h_, dt, nsteps, heat_scale, stages));
+  }
   std::vector<T> rise() const { return get<T>(FUS_TH_RISE); }
   std::vector<T> heat() const { return get<T>(FUS_TH_HEAT); }
   std::vector<double> dose() const { return get<double>(FUS_TH_DOSE); }  // CEM43, minutes
