@@ -163,6 +163,20 @@ void orc_dphi(int N, const double* nodes, double* D);
       const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0, const REAL* src,           \
       const REAL* absb, const REAL* src2, double freq, double p0, double s0, double t0, double tf, \
       double dt, REAL* u, REAL* v, double source_scale, int64_t nsteps);                           \
+  /* The two above with the explicit RK tables of orc_linear_rk (order 1..4); order 4 is what the    \
+   * rk4 entry points run. */                                                                       \
+  int64_t orc_lossy_rk_n_##SUF(int order, int tdim, int64_t ncells, int64_t ndofs, int N,          \
+                               const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,      \
+                               const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,        \
+                               const REAL* src, const REAL* absb, const REAL* src2, double freq,   \
+                               double p0, double s0, double t0, double tf, double dt, REAL* u,     \
+                               REAL* v, double source_scale, int64_t nsteps);                      \
+  int64_t orc_westervelt_rk_n_##SUF(                                                               \
+      int order, int tdim, int64_t ncells, int64_t ndofs, int N, const int32_t* tensor_dofmap,     \
+      const REAL* G, const REAL* detJ, const REAL* dphi, const REAL* lin_coeff,                    \
+      const REAL* att_coeff, const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,     \
+      const REAL* src, const REAL* absb, const REAL* src2, double freq, double p0, double s0,      \
+      double t0, double tf, double dt, REAL* u, REAL* v, double source_scale, int64_t nsteps);     \
   /* CPU-baseline variant of orc_linear_rk4 (3-D): nslabs threads, one contiguous cell slab each    \
    * (slab_cell_off[nslabs+1]); even/odd slab passes replace the interface scatter_rev. */          \
   int64_t orc_linear_rk4_mt_##SUF(int64_t ncells, int64_t ndofs, int N,                            \

@@ -653,6 +653,30 @@ static void FN(k_axpy)(int64_t n, REAL* r, REAL alpha, const REAL* x, const REAL
     r[i] = x[i] * alpha + y[i];
 }
 
+/* Butcher tables of the explicit steppers, strictly lower-bidiagonal (stage i reads stage i-1 only):
+ * order 4 = classical RK4 (Linear.hpp:263-265); 1, 2, 3 = forward Euler / Ralston tables of the
+ * Python reference's rk() (python/src/fenicsxfus/_linear.py:286-311, loop :461-499). */
+static void FN(rk_tables)(int order, REAL a_runge[4], REAL b_runge[4], REAL c_runge[4])
+{
+  a_runge[0] = 0.0, a_runge[1] = 0.5, a_runge[2] = 0.5, a_runge[3] = 1.0;
+  b_runge[0] = (REAL)(1.0 / 6.0), b_runge[1] = (REAL)(1.0 / 3.0), b_runge[2] = (REAL)(1.0 / 3.0);
+  b_runge[3] = (REAL)(1.0 / 6.0);
+  c_runge[0] = 0.0, c_runge[1] = 0.5, c_runge[2] = 0.5, c_runge[3] = 1.0;
+  if (order == 1)
+    a_runge[0] = 0, b_runge[0] = 1, c_runge[0] = 0;
+  else if (order == 2)
+  {
+    a_runge[1] = (REAL)(2.0 / 3.0), b_runge[0] = (REAL)(1.0 / 4.0), b_runge[1] = (REAL)(3.0 / 4.0);
+    c_runge[1] = (REAL)(2.0 / 3.0);
+  }
+  else if (order == 3)
+  {
+    a_runge[1] = (REAL)(1.0 / 2.0), a_runge[2] = (REAL)(3.0 / 4.0);
+    b_runge[0] = (REAL)(2.0 / 9.0), b_runge[1] = (REAL)(1.0 / 3.0), b_runge[2] = (REAL)(4.0 / 9.0);
+    c_runge[1] = (REAL)(1.0 / 2.0), c_runge[2] = (REAL)(3.0 / 4.0);
+  }
+}
+
 /* Linear.hpp:161-314.  Single process: scatter_fwd/scatter_rev (:196,199,206) are no-ops.
  * The FFCx facet assembly (:205) is the diagonal form  b += g(t) src - absb .* v_n. */
 /* order: 4 = classical RK4 (Linear.hpp:263-265); 1, 2, 3 = forward Euler / Ralston tables of the
@@ -681,22 +705,8 @@ int64_t FN(orc_linear_rk_n)(int order, int tdim, int64_t ncells, int64_t ndofs, 
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
-  REAL a_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  REAL b_runge[4] = {(REAL)(1.0 / 6.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 6.0)};
-  REAL c_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  if (order == 1)
-    a_runge[0] = 0, b_runge[0] = 1, c_runge[0] = 0;
-  else if (order == 2)
-  {
-    a_runge[1] = (REAL)(2.0 / 3.0), b_runge[0] = (REAL)(1.0 / 4.0), b_runge[1] = (REAL)(3.0 / 4.0);
-    c_runge[1] = (REAL)(2.0 / 3.0);
-  }
-  else if (order == 3)
-  {
-    a_runge[1] = (REAL)(1.0 / 2.0), a_runge[2] = (REAL)(3.0 / 4.0);
-    b_runge[0] = (REAL)(2.0 / 9.0), b_runge[1] = (REAL)(1.0 / 3.0), b_runge[2] = (REAL)(4.0 / 9.0);
-    c_runge[1] = (REAL)(1.0 / 2.0), c_runge[2] = (REAL)(3.0 / 4.0);
-  }
+  REAL a_runge[4], b_runge[4], c_runge[4];
+  FN(rk_tables)(order, a_runge, b_runge, c_runge);
   while (nsteps >= 0 ? step < nsteps : t < tf)
   {
     if (nsteps < 0)
@@ -777,13 +787,13 @@ int64_t FN(orc_linear_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
 /* source_scale: 2 = the live "heterogenous domain" branch of Lossy.hpp:216-220; 1 = the Python
  * package (python/src/fenicsxfus/_lossy.py:186-189), which also keeps the absorbing and delta-mass
  * terms on tag 2 only -- that choice is in the vectors the caller passes (absb, m). */
-/* nsteps: as orc_linear_rk_n */
-int64_t FN(orc_lossy_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
-                            const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
-                            const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
-                            const REAL* src, const REAL* absb, const REAL* src2, double freq_,
-                            double p0_, double s0_, double t0, double tf_, double dt_, REAL* u_n,
-                            REAL* v_n, double source_scale, int64_t nsteps)
+/* order, nsteps: as orc_linear_rk_n */
+int64_t FN(orc_lossy_rk_n)(int order, int tdim, int64_t ncells, int64_t ndofs, int N,
+                           const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
+                           const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
+                           const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                           double p0_, double s0_, double t0, double tf_, double dt_, REAL* u_n,
+                           REAL* v_n, double source_scale, int64_t nsteps)
 {
   const REAL two = (REAL)source_scale;
   const REAL freq = (REAL)freq_, p0 = (REAL)p0_, s0 = (REAL)s0_;
@@ -799,16 +809,14 @@ int64_t FN(orc_lossy_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
-  const REAL a_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  const REAL b_runge[4] = {(REAL)(1.0 / 6.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 3.0),
-                           (REAL)(1.0 / 6.0)};
-  const REAL c_runge[4] = {0.0, 0.5, 0.5, 1.0};
+  REAL a_runge[4], b_runge[4], c_runge[4];
+  FN(rk_tables)(order, a_runge, b_runge, c_runge);
   while (nsteps >= 0 ? step < nsteps : t < tf)
   {
     if (nsteps < 0)
       dt = (dt < tf - t) ? dt : tf - t;
     FN(k_copy)(ndofs, u_, u0), FN(k_copy)(ndofs, v_, v0);
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < order; i++)
     {
       FN(k_copy)(ndofs, u0, un), FN(k_copy)(ndofs, v0, vn);
       FN(k_axpy)(ndofs, un, dt * a_runge[i], ku, un);
@@ -860,6 +868,17 @@ int64_t FN(orc_lossy_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
   return step;
 }
 
+int64_t FN(orc_lossy_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
+                            const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
+                            const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
+                            const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                            double p0_, double s0_, double t0, double tf_, double dt_, REAL* u_n,
+                            REAL* v_n, double source_scale, int64_t nsteps)
+{
+  return FN(orc_lossy_rk_n)(4, tdim, ncells, ndofs, N, tensor_dofmap, G, dphi, lin_coeff, att_coeff, m,
+                            src, absb, src2, freq_, p0_, s0_, t0, tf_, dt_, u_n, v_n, source_scale, nsteps);
+}
+
 int64_t FN(orc_lossy_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,
                             const int32_t* tensor_dofmap, const REAL* G, const REAL* dphi,
                             const REAL* lin_coeff, const REAL* att_coeff, const REAL* m,
@@ -888,14 +907,14 @@ int64_t FN(orc_lossy_rk4)(int tdim, int64_t ncells, int64_t ndofs, int N,
  * M(nlin2) (v_n .* v_n)  (:246-247, :263, nlin2 = +2 beta/(rho^2 c^4), :186).  detJ is the scaled
  * Jacobian determinant the mass operator uses (spectral_op.hpp:80-81).  Other arguments as
  * orc_lossy_rk4 (m0 = its m). */
-/* nsteps: as orc_linear_rk_n */
-int64_t FN(orc_westervelt_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
-                                 const int32_t* tensor_dofmap, const REAL* G, const REAL* detJ,
-                                 const REAL* dphi, const REAL* lin_coeff, const REAL* att_coeff,
-                                 const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,
-                                 const REAL* src, const REAL* absb, const REAL* src2, double freq_,
-                                 double p0_, double s0_, double t0, double tf_, double dt_,
-                                 REAL* u_n, REAL* v_n, double source_scale, int64_t nsteps)
+/* order, nsteps: as orc_linear_rk_n */
+int64_t FN(orc_westervelt_rk_n)(int order, int tdim, int64_t ncells, int64_t ndofs, int N,
+                                const int32_t* tensor_dofmap, const REAL* G, const REAL* detJ,
+                                const REAL* dphi, const REAL* lin_coeff, const REAL* att_coeff,
+                                const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,
+                                const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                                double p0_, double s0_, double t0, double tf_, double dt_,
+                                REAL* u_n, REAL* v_n, double source_scale, int64_t nsteps)
 {
   const REAL two = (REAL)source_scale;
   const REAL freq = (REAL)freq_, p0 = (REAL)p0_, s0 = (REAL)s0_;
@@ -912,16 +931,14 @@ int64_t FN(orc_westervelt_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
   int64_t step = 0;
   FN(k_copy)(ndofs, u_n, u_), FN(k_copy)(ndofs, v_n, v_);
   FN(k_copy)(ndofs, u_, ku), FN(k_copy)(ndofs, v_, kv);
-  const REAL a_runge[4] = {0.0, 0.5, 0.5, 1.0};
-  const REAL b_runge[4] = {(REAL)(1.0 / 6.0), (REAL)(1.0 / 3.0), (REAL)(1.0 / 3.0),
-                           (REAL)(1.0 / 6.0)};
-  const REAL c_runge[4] = {0.0, 0.5, 0.5, 1.0};
+  REAL a_runge[4], b_runge[4], c_runge[4];
+  FN(rk_tables)(order, a_runge, b_runge, c_runge);
   while (nsteps >= 0 ? step < nsteps : t < tf)
   {
     if (nsteps < 0)
       dt = (dt < tf - t) ? dt : tf - t;
     FN(k_copy)(ndofs, u_, u0), FN(k_copy)(ndofs, v_, v0);
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < order; i++)
     {
       FN(k_copy)(ndofs, u0, un), FN(k_copy)(ndofs, v0, vn);
       FN(k_axpy)(ndofs, un, dt * a_runge[i], ku, un);
@@ -981,6 +998,19 @@ int64_t FN(orc_westervelt_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
   free(u_), free(v_), free(un), free(vn), free(u0), free(v0), free(ku), free(kv), free(b), free(uw),
       free(vw), free(ww), free(m);
   return step;
+}
+
+int64_t FN(orc_westervelt_rk4_n)(int tdim, int64_t ncells, int64_t ndofs, int N,
+                                 const int32_t* tensor_dofmap, const REAL* G, const REAL* detJ,
+                                 const REAL* dphi, const REAL* lin_coeff, const REAL* att_coeff,
+                                 const REAL* nlin1_coeff, const REAL* nlin2_coeff, const REAL* m0,
+                                 const REAL* src, const REAL* absb, const REAL* src2, double freq_,
+                                 double p0_, double s0_, double t0, double tf_, double dt_,
+                                 REAL* u_n, REAL* v_n, double source_scale, int64_t nsteps)
+{
+  return FN(orc_westervelt_rk_n)(4, tdim, ncells, ndofs, N, tensor_dofmap, G, detJ, dphi, lin_coeff,
+                                 att_coeff, nlin1_coeff, nlin2_coeff, m0, src, absb, src2, freq_, p0_,
+                                 s0_, t0, tf_, dt_, u_n, v_n, source_scale, nsteps);
 }
 
 int64_t FN(orc_westervelt_rk4_s)(int tdim, int64_t ncells, int64_t ndofs, int N,

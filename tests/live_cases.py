@@ -108,10 +108,10 @@ class Case:
         ns = self.nsteps if nsteps is None else nsteps
         tf = t0 + ns * self.dt * (1 + (margin if margin is not None else (1e-12 if exact else -1e-9)))
         a = (self.tdim, pr.N, pr.dm, pr.G)
-        kw = dict(dtype=dtype, steps=ns if fixed else None)
+        kw = dict(dtype=dtype, steps=ns if fixed else None, order=self.order if order is None else order)
         if self.kind == "linear":
             k = self.orc.linear_rk4(*a, pr.D, V["coeff"], V["m"], V["src"], V["absb"], F0, self.p0, S0, t0, tf,
-                                    self.dt, u, v, order=self.order if order is None else order, **kw)
+                                    self.dt, u, v, **kw)
         elif self.kind == "lossy":
             k = self.orc.lossy_rk4(*a, pr.D, V["coeff"], V["att"], V["m"], V["src"], V["absb"], V["src2"], F0, self.p0,
                                    S0, t0, tf, self.dt, u, v, **kw)
@@ -183,8 +183,38 @@ CASES["linear-q2"] = dict(kind="linear", n=(4, 3, 3), P=4, perturb=0.0, mesh_ord
                           warp=lambda x: x + np.c_[20.0 * x[:, 1] ** 2 - 12.0 * x[:, 2] ** 2, 15.0 * x[:, 2] ** 2,
                                                    0 * x[:, 0]])
 
-# ---- the fp32 cases held to the float oracle's own rounding error (fp32_budget.py) -----------------------------------
+# ---- the fp64 matrix (test_gpu_live_matrix.py): every family at every degree, perturbed cells and box ----------------
 KINDS = ("linear", "lossy", "westervelt")
+
+
+def _live_n(P, one_input=False):
+    """The smallest boxes whose guards pass, enlarged where ONE block of the whole mesh must give the stage epilogue
+    of k_block_op a second pass (more than 2 x ranges per pass x 256 threads interior DOFs, test_gpu_live_matrix.py):
+    degree 2 needs more than 512 DOFs (1024 with one operator input: two ranges per pass), (6, 5, 4) has 1287;
+    degree 3 with one input more than 1024, (5, 3, 2) has 1120 where (4, 3, 2) has 910."""
+    if P == 2:
+        return (6, 5, 4)
+    if P == 3 and one_input:
+        return (5, 3, 2)
+    return (4, 3, 2) if P <= 5 else ((3, 2, 2) if P <= 7 else (2, 2, 2))
+
+
+for _kind in KINDS:
+    for _P in (2, 3, 5, 6, 7, 8, 9, 10):
+        _kw = dict(kind=_kind, n=_live_n(_P, _kind == "linear"), P=_P, nsteps=10 if _P < 8 else 6)
+        CASES.setdefault(f"{_kind}-p{_P}", dict(_kw))
+        CASES[f"{_kind}-p{_P}-box"] = dict(_kw, perturb=0.0)
+for _P in (2, 3):          # linear-p2 / linear-p3 above keep their (4, 3, 2): too short for a second epilogue pass
+    CASES[f"linear-p{_P}-long"] = dict(kind="linear", n=_live_n(_P, True), P=_P)
+for _P, _n in ((4, (9, 7)), (9, (4, 3))):
+    CASES[f"lossy-quad-p{_P}"] = dict(kind="lossy", n=_n, P=_P)
+for _kind in KINDS:
+    for _o in (1, 2, 3):
+        CASES.setdefault(f"{_kind}-rk{_o}", dict(kind=_kind, n=(5, 4, 4), P=3, order=_o, cfl=0.1, nsteps=20))
+    for _o in (2, 3):      # the lower orders through the two-waves-per-element kernels
+        CASES[f"{_kind}-p8-rk{_o}"] = dict(kind=_kind, n=(2, 2, 2), P=8, order=_o, nsteps=6)
+
+# ---- the fp32 cases held to the float oracle's own rounding error (fp32_budget.py) -----------------------------------
 
 
 def _hex_n(P):

@@ -262,12 +262,14 @@ def test_two_models_on_one_op(orc, monkeypatch):
     cx.close()
 
 
-@pytest.mark.parametrize("kind", ["linear", "lossy", "westervelt"])
+@pytest.mark.parametrize("kind", ["linear", "lossy", "westervelt", "linear-p6-box", "lossy-p7", "westervelt-p9-box",
+                                  "lossy-rk2"])
 def test_negative_control_far_corner(orc, kind):
     """The GPU model with its family's coefficient (c0 / delta / beta) of the far-corner cells scaled by 1 + 1e-4
     must FAIL the comparison with the unchanged oracle by more than 100x the tolerance: the live start, set_state and
-    the comparison reach those DOFs."""
-    cs, u0, v0, ref = live_reference(orc, f"{kind}-p4")
+    the comparison reach those DOFs.  A family alone: its p=4 case; the named cases: one per path of
+    test_gpu_live_matrix.py (a box, two operator inputs at the degrees 7 and 9, a lower RK order)."""
+    cs, u0, v0, ref = live_reference(orc, kind if "-" in kind else f"{kind}-p4")
     cx = fa.Context(0)
     got = run_gpu(cs, cx, u0, v0, scale_far_corner=1 + 1e-4)
     assert relmax(got[0], ref[0]) > 100 * TOL_RK
