@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "layout.hpp"
 #include "sts_coef.hpp"
+#include "thermal_bc.hpp"
 #include "tables.hpp"
 
 using namespace fus;
@@ -2089,9 +2090,54 @@ struct fus_thermal
   void *kneg = nullptr;        // -k per cell, internal cell order
   double* dose = nullptr;      // CEM43 minutes, n_internal doubles
   double* d_stage = nullptr;   // ndofs doubles in caller numbering (dose in / out)
+  // boundary conditions (fus_thermal_set_boundary; lists: thermal_bc.hpp).  minv_bc: the copy of minv with zeros at the
+  // fixed DOFs that the stage and power kernels read while nfix > 0, allocated by the first call that fixes a DOF
+  void* minv_bc = nullptr;
+  int64_t nfix = 0, nconv = 0;
+  int32_t *fix_idx = nullptr, *conv_idx = nullptr;
+  void *fix_val = nullptr, *conv_hw = nullptr, *conv_r = nullptr;
+  std::vector<void*> bc_allocs;   // the five lists of the boundary in force
   std::vector<void*> allocs;
   bool initialised = false;
 };
+
+// 1 / m_C as the stage and power kernels take it: zero at the fixed DOFs while there are any
+static const void* thermal_minv(const fus_thermal* th) { return th->nfix > 0 ? th->minv_bc : th->minv; }
+
+// b += r - m_H x at the convective DOFs (r_too = false: the homogeneous part); nothing is enqueued without such DOFs
+template <typename T>
+static int thermal_robin(fus_thermal* th, const T* x, bool r_too)
+{
+  if (th->nconv == 0)
+    return FUS_OK;
+  ProfScope ps(th->ctx, "thermal_bc");
+  hipLaunchKernelGGL((k_thermal_robin<T>), dim3(nblk(th->nconv)), dim3(256), 0, th->ctx->stream, th->nconv,
+                     static_cast<const int32_t*>(th->conv_idx), static_cast<const T*>(th->conv_hw),
+                     r_too ? static_cast<const T*>(th->conv_r) : nullptr, x, static_cast<T*>(th->b));
+  HIPCHK(hipGetLastError());
+  return FUS_OK;
+}
+
+// vec = the fixed values (zero_values: 0) at the fixed DOFs; with_minv: minv_bc = 0 there as well.  Nothing is enqueued
+// without fixed DOFs
+template <typename T>
+static int thermal_impose(fus_thermal* th, T* vec, bool zero_values = false, bool with_minv = false)
+{
+  if (th->nfix == 0)
+    return FUS_OK;
+  ProfScope ps(th->ctx, "thermal_fix");
+  hipLaunchKernelGGL((k_thermal_fix<T>), dim3(nblk(th->nfix)), dim3(256), 0, th->ctx->stream, th->nfix,
+                     static_cast<const int32_t*>(th->fix_idx), zero_values ? nullptr : static_cast<const T*>(th->fix_val),
+                     vec, with_minv ? static_cast<T*>(th->minv_bc) : nullptr);
+  HIPCHK(hipGetLastError());
+  return FUS_OK;
+}
+
+template <typename T>
+static int thermal_impose_rise(fus_thermal* th)
+{
+  return thermal_impose<T>(th, static_cast<T*>(th->th0));
+}
 
 template <typename T>
 static int thermal_cells_to_internal(fus_thermal* th, const void* host_cells, T* out_i)
@@ -2186,11 +2232,12 @@ static int thermal_step(fus_thermal* th, double dt_, double sigma)
   {
     const T* x = static_cast<const T*>(i == 0 ? th->th0 : th->ths);
     FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, x, th->b));
+    FUSCHK(thermal_robin<T>(th, x, true));
     ThermalStage<T> A;
     A.b = static_cast<const T*>(th->b), A.th_in = x;
     A.th_out = static_cast<T*>(i == 3 ? th->th0 : th->ths);
     A.th0 = static_cast<const T*>(th->th0), A.acc = static_cast<T*>(th->acc);
-    A.minv = static_cast<const T*>(th->minv), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+    A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
     A.dose = th->dose;
     A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
     A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
@@ -2221,12 +2268,13 @@ static int thermal_step_sts(fus_thermal* th, double dt_, double sigma, const fus
   {
     const T* y1 = j == 1 ? th0 : rot[(j - 2) & 1];
     FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, y1, th->b));
+    FUSCHK(thermal_robin<T>(th, y1, true));
     ThermalSts<T> A;
     A.b = static_cast<const T*>(th->b), A.y1 = y1;
     A.y2 = j <= 2 ? th0 : rot[(j - 1) & 1];
     A.y0 = th0, A.f0 = static_cast<T*>(th->f0);
     A.out = j == c.s ? th0 : rot[(j - 1) & 1];
-    A.minv = static_cast<const T*>(th->minv), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+    A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
     A.dose = th->dose;
     A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
     A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
@@ -2240,7 +2288,9 @@ static int thermal_step_sts(fus_thermal* th, double dt_, double sigma, const fus
       hipLaunchKernelGGL((k_thermal_sts_stage<T, 2>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
     HIPCHK(hipGetLastError());
   }
-  return FUS_OK;
+  // a fixed DOF passes through mu Y + nu Y + om Y in every stage, which returns Y only up to rounding (RK4's stages add
+  // an exact zero instead): one sparse launch per step puts the values back, so that they hold exactly here too
+  return thermal_impose<T>(th, th0);
 }
 
 // h = M(qcoef_i) 1 .* q: q a T vector in internal numbering (q_i), or Q / nsamp from the monitor's plane (Q)
@@ -2366,6 +2416,8 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
         src = tc;
       }
       hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, src, vec);
+      HIPCHK(hipGetLastError());
+      FUSCHK(thermal_impose<T>(th, vec));   // the rise: fus_thermal_set refuses FUS_TH_HEAT
     }
     else
     {
@@ -2381,8 +2433,9 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
   return FUS_OK;
 }
 
-// Power iteration for lambda_max of m_C^-1 (K(k) + diag m_W).  Setup-time work: the operator and the quotient
-// y = (K(k) x + m_W x) / m_C run on the device, y is pulled, the three m_C-weighted dot products and the normalisation
+// Power iteration for lambda_max of m_C^-1 (K(k) + diag(m_W + m_H)) with the rows and columns of the fixed DOFs removed
+// (the start vector is zero there, and so is every iterate: minv_bc).  Setup-time work: the operator and the quotient
+// y = (K(k) x + m_W x + m_H x) / m_C run on the device, y is pulled, the three m_C-weighted dot products and the normalisation
 // are done on the host in double, and the next x is pushed back.
 template <typename T>
 static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
@@ -2399,6 +2452,8 @@ static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
   HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(T), st));
   HIPCHK(hipMemcpyAsync(tc, xc.data(), nd * sizeof(T), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, static_cast<const T*>(tc), xd);
+  HIPCHK(hipGetLastError());
+  FUSCHK(thermal_impose<T>(th, xd, true));
   std::vector<T> x(n), y(n), mc(n);
   HIPCHK(hipMemcpyAsync(x.data(), xd, n * sizeof(T), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(mc.data(), th->mc, n * sizeof(T), hipMemcpyDeviceToHost, st));
@@ -2407,8 +2462,9 @@ static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
   for (int it = 0; it < iters; ++it)
   {
     FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, xd, th->b));
+    FUSCHK(thermal_robin<T>(th, xd, false));
     hipLaunchKernelGGL((k_thermal_power<T>), dim3(1024), dim3(256), 0, st, n, static_cast<const T*>(th->b),
-                       static_cast<const T*>(xd), static_cast<const T*>(th->mw), static_cast<const T*>(th->minv), yd);
+                       static_cast<const T*>(xd), static_cast<const T*>(th->mw), static_cast<const T*>(thermal_minv(th)), yd);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(y.data(), yd, n * sizeof(T), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2433,6 +2489,60 @@ static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
   HIPCHK(hipMemsetAsync(yd, 0, n * sizeof(T), st));
   HIPCHK(hipStreamSynchronize(st));
   *lambda = rho;
+  return FUS_OK;
+}
+
+// Replaces the boundary: the lists are built and validated on the host (thermal_bc.hpp), uploaded into buffers of their own
+// and only then put in force, so that an error leaves the previous boundary as it was.
+template <typename T>
+static int thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
+                                const void* conv_rise)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal;
+  fus::ThermalBcLists<T> L;
+  const int err = fus::thermal_bc_lists<T>(op->ndofs, op->L.dof_perm.data(), fixed, static_cast<const T*>(fixed_rise),
+                                           static_cast<const T*>(conv_diag), static_cast<const T*>(conv_rise), &L);
+  if (err != fus::TBC_OK)
+    return fail(FUS_ERR_ARG, std::string("fus_thermal_set_boundary: ") + fus::thermal_bc_message(err));
+  std::vector<void*> fresh;
+  int32_t *fi = nullptr, *ci = nullptr;
+  T *fv = nullptr, *hw = nullptr, *r = nullptr;
+  int rc = FUS_OK;
+  if (!L.fix_idx.empty())
+  {
+    rc = rc != FUS_OK ? rc : upload(fresh, &fi, L.fix_idx, st);
+    rc = rc != FUS_OK ? rc : upload(fresh, &fv, L.fix_val, st);
+    if (rc == FUS_OK && !th->minv_bc)
+      rc = dalloc_bytes(th->allocs, &th->minv_bc, n * sizeof(T), false, st);
+  }
+  if (!L.conv_idx.empty())
+  {
+    rc = rc != FUS_OK ? rc : upload(fresh, &ci, L.conv_idx, st);
+    rc = rc != FUS_OK ? rc : upload(fresh, &hw, L.hw, st);
+    rc = rc != FUS_OK ? rc : upload(fresh, &r, L.r, st);
+  }
+  if (rc == FUS_OK && hipStreamSynchronize(st) != hipSuccess)   // the uploads read L
+    rc = fail(FUS_ERR_HIP, "fus_thermal_set_boundary: stream synchronisation failed");
+  if (rc != FUS_OK)
+  {
+    for (void* q : fresh)
+      (void)hipFree(q);
+    return rc;
+  }
+  for (void* q : th->bc_allocs)   // every step that read them has finished: the step calls synchronise
+    (void)hipFree(q);
+  th->bc_allocs = std::move(fresh);
+  th->nfix = (int64_t)L.fix_idx.size(), th->nconv = (int64_t)L.conv_idx.size();
+  th->fix_idx = fi, th->fix_val = fv, th->conv_idx = ci, th->conv_hw = hw, th->conv_r = r;
+  if (th->nfix > 0)
+  {
+    HIPCHK(hipMemcpyAsync(th->minv_bc, th->minv, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    // the rise of an object not yet initialised is rewritten by fus_thermal_init / fus_thermal_set, which impose again
+    FUSCHK(thermal_impose<T>(th, static_cast<T*>(th->th0), false, true));
+    HIPCHK(hipStreamSynchronize(st));
+  }
   return FUS_OK;
 }
 
@@ -3697,6 +3807,8 @@ int fus_thermal_destroy(fus_thermal* th)
   (void)hipStreamSynchronize(th->ctx->stream);
   for (void* q : th->allocs)
     (void)hipFree(q);
+  for (void* q : th->bc_allocs)
+    (void)hipFree(q);
   delete th;
   return FUS_OK;
 }
@@ -3710,6 +3822,7 @@ int fus_thermal_init(fus_thermal* th)
   for (void* v : {th->th0, th->ths, th->acc})
     HIPCHK(hipMemsetAsync(v, 0, n * th->op->ts, th->ctx->stream));
   HIPCHK(hipMemsetAsync(th->dose, 0, n * sizeof(double), th->ctx->stream));
+  FUSCHK(FUS_TH_CALL(th, thermal_impose_rise, th));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
   th->initialised = true;
   return FUS_OK;
@@ -3803,6 +3916,26 @@ int fus_thermal_steps_sts(fus_thermal* th, double dt, int64_t nsteps, double hea
   for (int64_t s = 0; s < nsteps; ++s)
     FUSCHK(FUS_TH_CALL(th, thermal_step_sts, th, dt, heat_scale, coef));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
+                             const void* conv_rise)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_boundary: null argument");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_set_boundary, th, fixed, fixed_rise, conv_diag, conv_rise);
+}
+
+int fus_thermal_boundary_info(fus_thermal* th, int64_t* nfixed, int64_t* nconvective)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_boundary_info: null argument");
+  if (nfixed)
+    *nfixed = th->nfix;
+  if (nconvective)
+    *nconvective = th->nconv;
   return FUS_OK;
 }
 

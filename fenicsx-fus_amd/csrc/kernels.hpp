@@ -3839,6 +3839,45 @@ __global__ void k_thermal_power(int64_t n, const T* __restrict__ b, const T* __r
     y[i] = (mw[i] * x[i] - b[i]) * minv[i];
 }
 
+// ---- boundary conditions of the bioheat model (fus_thermal_set_boundary; entry lists: thermal_bc.hpp) ----
+// Both conditions are diagonal on the GLL-collocated space, so the stage kernels above stay as they are and the device
+// work is proportional to the surface: sparse lists of internal DOF indices, unique and ascending (neighbouring lanes hit
+// neighbouring lines), one thread per entry, every access at k or idx[k], no atomics, no LDS.
+//
+// Convective (Robin) faces, -k dtheta/dn = h_c (theta - theta_ext): with hw = m_H = sum_facets h_c |J_f| w_a w_b and
+// r = m_H theta_ext, the surface term joins the operator result between the shared reduction and the stage kernel,
+//   b[idx[k]] += r[k] - hw[k] x[idx[k]],
+// x the vector the operator was applied to.  r == nullptr: the homogeneous part (the power iteration, whose
+// y = (m_W x - b) / m_C thereby gains m_H x).
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_thermal_robin(int64_t nr, const int32_t* __restrict__ idx, const T* __restrict__ hw, const T* __restrict__ r,
+                const T* __restrict__ x, T* __restrict__ b)
+{
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= nr)
+    return;
+  const int32_t i = idx[k];
+  b[i] += (r ? r[k] : T(0)) - hw[k] * x[i];
+}
+
+// Fixed (Dirichlet) DOFs: theta[idx[k]] = val[k] (val == nullptr: 0).  With minv_bc != nullptr also minv_bc[idx[k]] = 0:
+// the stage kernels and the power kernel read that copy of 1 / m_C in place of the original, so the stage derivative
+// vanishes at a fixed DOF exactly as it does in a padding slot, and no mask is read in the streaming loops.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_thermal_fix(int64_t nf, const int32_t* __restrict__ idx, const T* __restrict__ val, T* __restrict__ theta,
+              T* __restrict__ minv_bc)
+{
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= nf)
+    return;
+  const int32_t i = idx[k];
+  theta[i] = val ? val[k] : T(0);
+  if (minv_bc)
+    minv_bc[i] = T(0);
+}
+
 // halo helpers
 // pack: sendbuf[k] = vec[idx[k]] over the concatenated neighbour lists
 // Receiver sampling (the reference evaluates its solution at points with Function::eval after locating their cells:

@@ -2,14 +2,16 @@
 
 ``BioheatSpectralExplicit`` advances the temperature rise ``theta = T - t_base`` of
 
-    rho C dtheta/dt = div(k grad theta) - W theta + Q        (insulating boundaries)
+    rho C dtheta/dt = div(k grad theta) - W theta + Q
 
 with classical RK4 on the GPU, or with the super-time-stepping scheme RKL2 (``steps(..., stages=s)``: s operator
 applications per step, a step about ``(s^2 + s - 2) / 5.6`` times the RK4 step), and accumulates the thermal dose in
 cumulative equivalent minutes at 43 degrees C.  The
 heat load comes from a nodal field (:meth:`set_heat`) or, without leaving the device, from the field monitor of a wave
-model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``.  The reference package
-has no thermal model; this module replaces nothing there."""
+model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``.  Every face is
+insulating until :meth:`BioheatSpectralExplicit.set_boundary` holds it at a temperature (a cut face in tissue) or lets it
+exchange heat with a coolant (water-cooled skin).  The reference package has no thermal model; this module replaces
+nothing there."""
 from __future__ import annotations
 
 import ctypes as C
@@ -150,15 +152,82 @@ class BioheatSpectralExplicit:
         a = self._cells(absorption, "absorption")
         check(lib().fus_thermal_set_heat_from_monitor(self.h, model.h, ptr(a)))
 
+    def set_boundary(self, tags, fixed=None, convective=None):
+        """Boundary conditions on tagged facets; every other face stays insulating, and any boundary set before is
+        replaced.  ``tags``: a :class:`FacetTags` / DOLFINx-style mesh-tags object, as the wave models take it.
+        ``fixed``: ``{tag: temperature}`` in degrees C, a scalar or one value per DOF (read on the face) -- the DOFs of
+        those facets are held there.  ``convective``: ``{tag: (h_c, coolant temperature)}``, ``h_c`` >= 0 in W/m^2/K, a
+        scalar or one value per cell (the facet takes its cell's), the temperature in degrees C, a scalar or one value
+        per DOF: ``-k dT/dn = h_c (T - T_coolant)``.  A DOF on both kinds of face is fixed; where two convective faces
+        meet their terms add, the coolant temperature being the average weighted by them."""
+        nd, dt = self.data.ndofs, self.dtype
+        cells, lf = np.asarray(tags.cells), np.asarray(tags.local_facets)
+        values = np.asarray(tags.values)
+
+        def diag(tag, coef):
+            sel = np.flatnonzero(values == tag)
+            if not len(sel):
+                raise _abi.FusError(f"set_boundary: no facet carries the tag {tag}")
+            return self.data.facet_diag(cells[sel], lf[sel], self._cells(coef, "h_c")).astype(np.float64)
+
+        def rises(temp, name):
+            a = np.asarray(_array(temp), dtype=np.float64)
+            if a.ndim and a.shape != (nd,):
+                raise _abi.FusError(f"{name}: expected a scalar or {nd} values, one per DOF, got shape {a.shape}")
+            return np.broadcast_to(a - self.t_base, (nd,))
+
+        mask = rise = m_h = r = None
+        if fixed:
+            mask, rise = np.zeros(nd, np.uint8), np.zeros(nd, np.float64)
+            for tag, temp in fixed.items():
+                on = diag(tag, 1.0) > 0.0
+                mask[on] = 1
+                rise[on] = rises(temp, "fixed temperature")[on]
+        if convective:
+            parts = [(diag(tag, h_c), rises(temp, "coolant temperature")) for tag, (h_c, temp) in convective.items()]
+            m_h = np.sum([m for m, _ in parts], axis=0)
+            faces = np.sum([m > 0.0 for m, _ in parts], axis=0)
+            # several faces at a DOF: the average of their coolants' rises weighted by their terms; one face: its
+            # coolant's rise as given (m theta / m need not return theta)
+            r = np.divide(np.sum([m * ext for m, ext in parts], axis=0), m_h, out=np.zeros(nd), where=faces > 1)
+            for m, ext in parts:
+                on = (faces == 1) & (m > 0.0)
+                r[on] = ext[on]
+        self.set_boundary_arrays(mask, None if rise is None else rise.astype(dt),
+                                 None if m_h is None else m_h.astype(dt), None if r is None else r.astype(dt))
+
+    def set_boundary_arrays(self, fixed=None, fixed_rise=None, conv_diag=None, conv_rise=None):
+        """The boundary per DOF (fus_thermal_set_boundary): ``fixed`` a mask (nonzero = held at ``fixed_rise``, K over
+        ``t_base``; None = 0), ``conv_diag`` = m_H >= 0, the facet diagonal of h_c (``data.facet_diag`` with the
+        coefficient h_c, summed over the convective faces), ``conv_rise`` the coolant's rise over ``t_base`` (None = 0).
+        Replaces any boundary set before; all None clears it."""
+        fa = None if fixed is None else self._dofs(np.asarray(_array(fixed)) != 0, "fixed", np.uint8)
+        fr = None if fixed_rise is None else self._dofs(fixed_rise, "fixed_rise")
+        cd = None if conv_diag is None else self._dofs(conv_diag, "conv_diag")
+        cr = None if conv_rise is None else self._dofs(conv_rise, "conv_rise")
+        check(lib().fus_thermal_set_boundary(self.h, ptr(fa), ptr(fr), ptr(cd), ptr(cr)))
+
+    def clear_boundary(self):
+        """Back to insulating faces everywhere: steps then run exactly as on an object that never had a boundary."""
+        check(lib().fus_thermal_set_boundary(self.h, None, None, None, None))
+
+    def boundary_info(self):
+        """``(number of fixed DOFs, number of convective DOFs)`` in force."""
+        nf, nc = C.c_int64(), C.c_int64()
+        check(lib().fus_thermal_boundary_info(self.h, C.byref(nf), C.byref(nc)))
+        return nf.value, nc.value
+
     def lambda_max(self, iters: int = 20) -> float:
         """Rayleigh quotient after ``iters`` power iterations: a lower bound of the largest eigenvalue of
-        ``m_C^-1 (K(k) + diag m_W)`` (1/s)."""
+        ``m_C^-1 (K(k) + diag(m_W + m_H))`` (1/s) with the rows and columns of the fixed DOFs removed -- m_H the
+        convective faces' diagonal, zero without :meth:`set_boundary`."""
         out = C.c_double()
         check(lib().fus_thermal_lambda_max(self.h, C.c_int(iters), C.byref(out)))
         return out.value
 
     def stable_dt(self, stages: int = 0) -> float:
-        """``stages`` = 0: ``2 / lambda_max(20)``, inside the RK4 limit 2.785 / lambda_max while the quotient has reached
+        """Of the operator :meth:`lambda_max` names, the boundary in force included (a water-cooled face shortens the
+        step).  ``stages`` = 0: ``2 / lambda_max(20)``, inside the RK4 limit 2.785 / lambda_max while the quotient has reached
         0.72 of it.  ``stages`` = s in 2..32: ``0.72 (s^2 + s - 2) / (2 lambda_max(20))``, inside the RKL2 limit
         (s^2 + s - 2) / (2 lambda_max) with the same margin, under the same condition."""
         out = C.c_double()

@@ -355,7 +355,8 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  *
  * State: the temperature RISE theta = T - t_base over a uniform baseline t_base (arterial and initial temperature,
  * degrees C); the rise and not the temperature, so that FUS_F32 objects do not lose a 0.01 K increment against 37.
- *   rho C dtheta/dt = div(k grad theta) - W theta + Q,     natural (insulating) boundaries
+ *   rho C dtheta/dt = div(k grad theta) - W theta + Q,     natural (insulating) boundaries unless
+ *                                                          fus_thermal_set_boundary sets others (below)
  * Per-cell coefficients, host T[ncells] in caller cell numbering: conductivity k >= 0 (W/m/K), rho_c > 0 (J/m^3/K),
  * perfusion W = w_b rho_b C_b >= 0 (W/m^3/K; NULL = 0).  On the GLL-collocated space of the wave models, with the
  * library's K(c) and M(c) (u^T K(1) u = integral of |grad u|^2):
@@ -392,11 +393,34 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  * RK4 steps and super-steps of any stage count may follow each other on one object.
  * fus_thermal_stable_dt: stages = 0 gives the RK4 step 2 / rho_iters; stages = s in 2..32 gives 0.72 beta_s / rho_iters,
  * the same margin (0.72 = 2 / 2.785) and safe under the same condition, rho_iters >= 0.72 lambda_max.
+ * Boundary conditions (fus_thermal_set_boundary): every face is insulating until a DOF is declared
+ *   fixed        theta = theta_D, a given nodal rise over t_base (a cut face in tissue at body temperature: 0), or
+ *   convective   -k dtheta/dn = h_c (theta - theta_ext): h_c >= 0 in W/m^2/K, theta_ext the coolant's rise over t_base
+ *                (negative for cold water).
+ * Both are diagonal on the collocated space.  The caller passes per-DOF host arrays in its own numbering: a mask `fixed`
+ * with the values fixed_rise, and conv_diag = m_H = sum over the convective facets of h_c |J_f| w_a w_b -- what
+ * fus_facet_diag returns for cellcoef = h_c, summed over the faces -- with conv_rise = theta_ext.  With r = m_H .* theta_ext,
+ * formed in double and rounded to T once,
+ *   f(theta) = ( K(-k) theta - m_W .* theta - m_H .* theta + r + sigma h ) ./ m_C     at the free DOFs
+ *   f(theta) = 0,  theta = theta_D                                                   at the fixed DOFs
+ * r is NOT scaled by sigma: the coolant keeps working while the beam is off.  A DOF both fixed and convective is fixed; the
+ * heat load at a fixed DOF is ignored; the dose keeps accumulating there from the fixed temperature.  The fixed values hold
+ * exactly through every step of either scheme.  fus_thermal_lambda_max and fus_thermal_stable_dt then work on
+ * m_C^-1 (K(k) + diag(m_W + m_H)) with the rows and columns of the fixed DOFs removed (x_d = 0 and y = 0 there), which is
+ * still symmetric and non-negative in the m_C inner product, so both step rules apply unchanged -- and are needed: a
+ * water-cooled face (h_c = 5000) puts dt max(m_H / m_C) above 2 at the insulating operator's step.
+ * Cost: the lists are sparse, proportional to the surface.  Convective DOFs add one small launch per operator application
+ * (profile name "thermal_bc"); fixed DOFs add none to an RK4 step (the stage kernels read a copy of 1 / m_C that is zero
+ * there, as it is in the padding slots) and one per RKL2 step, which puts the values back after the stages' weighted sums
+ * (profile name "thermal_fix", also counted when fus_thermal_init / fus_thermal_set / fus_thermal_set_boundary /
+ * fus_thermal_lambda_max write them).  With no boundary set, or after clearing it, a step enqueues exactly the launches of
+ * an object that never had one, with the same arguments.
  *
  *   fus_thermal_create   on an existing operator object, also one created with "fields" = 2; several thermal objects and wave
  *                        models may share one op and run in turns on the context's stream
- *   fus_thermal_init     theta = 0, D = 0
- *   fus_thermal_set      which = FUS_TH_RISE: T[ndofs]; FUS_TH_DOSE: double[ndofs]; caller numbering, `space`
+ *   fus_thermal_init     theta = 0 (fixed DOFs: their values), D = 0
+ *   fus_thermal_set      which = FUS_TH_RISE: T[ndofs] (fixed DOFs take their values again); FUS_TH_DOSE: double[ndofs];
+ *                        caller numbering, `space`
  *   fus_thermal_get      FUS_TH_RISE, FUS_TH_HEAT (= h): T[ndofs]; FUS_TH_DOSE: double[ndofs]
  *   fus_thermal_set_heat q: T[ndofs], q_coef: T[ncells] or NULL (= 1), both in `space`; q == NULL: h = 0
  *   fus_thermal_set_heat_from_monitor   h from the field monitor of a wave model on the SAME fus_op, without leaving
@@ -407,10 +431,15 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  *   fus_thermal_steps_sts   nsteps RKL2 steps of `stages` stages each; states and argument checks as fus_thermal_steps,
  *                        and FUS_ERR_ARG for stages outside 2..32
  *   fus_thermal_stable_dt   lambda_max(iters) turned into a step for RK4 (stages = 0) or RKL2 (stages in 2..32)
+ *   fus_thermal_set_boundary   replaces any boundary set before; all arrays NULL clears it.  Before or after
+ *                        fus_thermal_init; theta at the fixed DOFs is overwritten at once.  fus_thermal_get(FUS_TH_HEAT)
+ *                        is unchanged
+ *   fus_thermal_boundary_info  the number of fixed and of convective DOFs in force (either pointer may be NULL)
  * Errors; argument and call-sequence errors (FUS_ERR_ARG, FUS_ERR_STATE) are found before anything is enqueued and leave the
  * state and the heat load as they were.  A FUS_ERR_HIP inside fus_thermal_steps returns at the failing step: the steps before
  * it have been applied and the stream is not synchronised.  FUS_ERR_ARG: null arguments; rho_c <= 0, a negative or
- * non-finite k, W or alpha; dt <= 0; iters < 1; stages outside 2..32 (fus_thermal_stable_dt: 0 or 2..32); a fus_model on
+ * non-finite k, W, alpha or conv_diag entry; a non-finite fixed_rise where fixed is set or conv_rise where conv_diag > 0;
+ * conv_rise without conv_diag (these leave the previous boundary in force); dt <= 0; iters < 1; stages outside 2..32 (fus_thermal_stable_dt: 0 or 2..32); a fus_model on
  * another fus_op than the thermal object's.  FUS_ERR_STATE:
  * steps before fus_thermal_init / fus_thermal_set; fus_thermal_stable_dt on a zero operator (k = 0 and W = 0 everywhere:
  * every step is stable); fus_thermal_set_heat_from_monitor while the model's monitor is off,
@@ -430,6 +459,12 @@ int fus_thermal_lambda_max(fus_thermal* thermal, int iters, double* lambda);
 int fus_thermal_steps(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale);
 int fus_thermal_steps_sts(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale, int stages);
 int fus_thermal_stable_dt(fus_thermal* thermal, int iters, int stages, double* dt);
+/* host arrays, caller DOF numbering; any of them may be NULL (fixed == NULL: no fixed DOF; conv_diag == NULL:
+ * no convective DOF; fixed_rise / conv_rise == NULL: 0).  Replaces any boundary set before; all NULL clears it. */
+int fus_thermal_set_boundary(fus_thermal* thermal, const uint8_t* fixed /* [ndofs], != 0: fixed */,
+                             const void* fixed_rise /* T[ndofs], read where fixed */,
+                             const void* conv_diag /* T[ndofs] = m_H >= 0 */, const void* conv_rise /* T[ndofs] */);
+int fus_thermal_boundary_info(fus_thermal* thermal, int64_t* nfixed, int64_t* nconvective);
 
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
@@ -463,7 +498,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
  * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform),
  * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared"), "thermal_sts" (the
- * same for a super-time-stepping stage).  total_ms/count accumulate since the last enable.
+ * same for a super-time-stepping stage), "thermal_bc" (convective surface term, once per operator application of a
+ * bioheat object with convective DOFs), "thermal_fix" (writes of the fixed values).  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

@@ -27,6 +27,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fusmi.h"
@@ -392,6 +393,7 @@ public:
   {
     check(fus_thermal_set_heat_from_monitor(h_, model.handle(), absorption));
   }
+  // of m_C^-1 (K(k) + diag(m_W + m_H)) with the fixed DOFs removed (the boundary in force)
   double lambda_max(int iters = 20) const
   {
     double l = 0;
@@ -409,6 +411,22 @@ public:
   {
     check(stages == 0 ? fus_thermal_steps(h_, dt, nsteps, heat_scale)
                       : fus_thermal_steps_sts(h_, dt, nsteps, heat_scale, stages));
+  }
+  // Boundary conditions, per-DOF arrays in caller numbering, any of them nullptr (fusmi.h "bioheat"): fixed[d] != 0 holds
+  // the DOF at the rise fixed_rise[d]; conv_diag = m_H, the facet diagonal of the heat-transfer coefficient h_c
+  // (fus_facet_diag on the operator's handle with cellcoef = h_c, summed over the convective faces), conv_rise the coolant's rise
+  // over t_base.  Replaces any boundary set before; every other face stays insulating.
+  void set_boundary(const std::uint8_t* fixed, const T* fixed_rise, const T* conv_diag, const T* conv_rise)
+  {
+    check(fus_thermal_set_boundary(h_, fixed, fixed_rise, conv_diag, conv_rise));
+  }
+  void clear_boundary() { check(fus_thermal_set_boundary(h_, nullptr, nullptr, nullptr, nullptr)); }
+  // (number of fixed DOFs, number of convective DOFs) in force
+  std::pair<std::int64_t, std::int64_t> boundary_info() const
+  {
+    std::int64_t nf = 0, nc = 0;
+    check(fus_thermal_boundary_info(h_, &nf, &nc));
+    return {nf, nc};
   }
   std::vector<T> rise() const { return get<T>(FUS_TH_RISE); }
   std::vector<T> heat() const { return get<T>(FUS_TH_HEAT); }

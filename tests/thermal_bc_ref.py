@@ -1,0 +1,150 @@
+"""Reference of the bioheat boundary-condition tests (fusmi.h "bioheat", fus_thermal_set_boundary), in numpy on
+thermal_ref.Bioheat: with m_H = sum over the convective facets of h_c |J_f| w_a w_b (util.Problem.facet_diag with the
+cell coefficient h_c) and r = m_H .* theta_ext,
+
+    f(theta) = (K(-k) theta - m_W .* theta - m_H .* theta + r + sigma h) ./ m_C     at the free DOFs
+    f(theta) = 0,  theta = theta_D                                                 at the fixed DOFs
+
+r is not scaled by sigma; a DOF both fixed and convective is fixed.  The power iteration runs on
+m_C^-1 (K(k) + diag(m_W + m_H)) with the rows and columns of the fixed DOFs removed.  ``BioheatBC`` overrides ``f``,
+``start_vector`` and ``power_iteration`` only, so ``Bioheat.run`` and ``sts_ref.step`` / ``run`` work on it unchanged from
+a start that carries the fixed values (``impose``).  Also the standard boundary the device tests share."""
+import functools
+
+import numpy as np
+
+from fenicsxfus_amd import FacetTags
+from thermal_ref import BONE, Bioheat, case, materials
+
+T_BASE = 37.0
+FIXED, CONV_X, CONV_Y = 1, 2, 3            # tags of the standard boundary: x = lo, x = hi, y = lo
+THETA_EXT = -17.0                           # water at 20 degrees C
+
+
+class BioheatBC(Bioheat):
+    """``fixed``: bool mask per DOF, ``fixed_rise``: the values there (read where fixed), ``m_h`` >= 0 and ``theta_ext``
+    per DOF (or scalars); None: none of that kind."""
+
+    def __init__(self, pr, k, rho_c, w=None, fixed=None, fixed_rise=None, m_h=None, theta_ext=None):
+        super().__init__(pr, k, rho_c, w)
+        n = pr.ndofs
+        full = lambda a: np.broadcast_to(np.asarray(0.0 if a is None else a, dtype=np.float64), (n,)).copy()   # noqa: E731
+        self.fixed = np.zeros(n, bool) if fixed is None else np.asarray(fixed).astype(bool)
+        self.fixed_rise = np.where(self.fixed, full(fixed_rise), 0.0)
+        self.m_h = np.where(self.fixed, 0.0, full(m_h))
+        self.r = self.m_h * full(theta_ext)
+        assert (self.m_h >= 0).all()
+
+    def impose(self, theta):
+        return np.where(self.fixed, self.fixed_rise, np.asarray(theta, dtype=np.float64))
+
+    def f(self, theta, h=None, sigma=1.0):
+        r = self.pr.K(theta, -self.k) - self.m_w * theta - self.m_h * theta + self.r
+        if h is not None and sigma != 0.0:
+            r = r + sigma * h
+        return np.where(self.fixed, 0.0, r / self.m_c)
+
+    def start_vector(self):
+        return np.where(self.fixed, 0.0, super().start_vector())
+
+    def apply(self, x):
+        """m_C^-1 (K(k) + diag(m_W + m_H)) x on the free DOFs, 0 on the fixed ones (x is zero there)."""
+        return np.where(self.fixed, 0.0, (self.pr.K(x, self.k) + (self.m_w + self.m_h) * x) / self.m_c)
+
+    def power_iteration(self, iters=20, x0=None):
+        x = self.start_vector() if x0 is None else np.where(self.fixed, 0.0, np.asarray(x0, dtype=np.float64))
+        rho = 0.0
+        for _ in range(iters):
+            y = self.apply(x)
+            rho = (x @ (self.m_c * y)) / (x @ (self.m_c * x))
+            x = y / np.sqrt(y @ (self.m_c * y))
+        return float(rho)
+
+    def dense_lambda_max(self):
+        """Largest eigenvalue of the dense symmetric m_C^-1/2 (K(k) + m_W + m_H) m_C^-1/2 on the free DOFs."""
+        n = self.pr.ndofs
+        A = np.empty((n, n))
+        e = np.zeros(n)
+        for j in range(n):
+            e[j] = 1.0
+            A[:, j] = self.pr.K(e, self.k)
+            e[j] = 0.0
+        A += np.diag(self.m_w + self.m_h)
+        s = 1.0 / np.sqrt(self.m_c)
+        A = s[:, None] * A * s[None, :]
+        free = ~self.fixed
+        A = A[np.ix_(free, free)]
+        return float(np.linalg.eigvalsh(0.5 * (A + A.T))[-1])
+
+
+def face_tags(mesh, faces):
+    """FacetTags with ``faces`` = {tag: (axis, side)}: side 0 = lo, 1 = hi."""
+    cells, lf, ax, sd = mesh.exterior_facets()
+    cs, ls, vs = [], [], []
+    for tag, (a, s) in faces.items():
+        sel = (ax == a) & (sd == s)
+        cs.append(cells[sel]), ls.append(lf[sel]), vs.append(np.full(int(sel.sum()), tag, np.int32))
+    return FacetTags(np.concatenate(cs), np.concatenate(ls), np.concatenate(vs))
+
+
+def face_dofs(pr, tags, tag):
+    """Bool mask of the DOFs on the facets of ``tag``."""
+    return pr.facet_diag(tags, tag, np.ones(pr.mesh.num_cells, pr.dtype)) > 0
+
+
+class Boundary:
+    """A boundary of thermal_ref case ``cs`` in both forms: what BioheatSpectralExplicit.set_boundary takes (``tags``,
+    ``fixed``, ``convective``: temperatures in degrees C) and what the reference takes (``mask``, ``rise``, ``m_h``,
+    ``theta_ext`` in double, the values the library ends up with after its rounding to the case's scalar type).
+    ``fixed``: {tag: rise per DOF or scalar}, ``convective``: {tag: (h_c per cell or scalar, theta_ext)}."""
+
+    def __init__(self, cs, faces, fixed=None, convective=None):
+        pr, t = cs.pr, cs.dtype
+        n = pr.ndofs
+        self.tags = face_tags(cs.prt.mesh, faces)
+        self.mask, self.rise = np.zeros(n, bool), np.zeros(n)
+        self.fixed, self.convective = {}, {}
+        for tag, rise in (fixed or {}).items():
+            on = face_dofs(pr, self.tags, tag)
+            temp = (T_BASE + np.broadcast_to(np.asarray(rise, dtype=np.float64), (n,))).copy()
+            self.fixed[tag] = temp
+            self.mask |= on
+            self.rise[on] = (temp - T_BASE).astype(t).astype(np.float64)[on]    # as set_boundary forms and rounds it
+        self.m_h = np.zeros(n)
+        for tag, (h_c, ext) in (convective or {}).items():
+            hc = np.broadcast_to(np.asarray(h_c, dtype=np.float64), (pr.mesh.num_cells,)).copy()
+            self.convective[tag] = (hc.astype(t), T_BASE + ext)
+            self.m_h += pr.facet_diag(self.tags, tag, hc)
+            self.theta_ext = float(ext)                                          # one coolant per boundary
+        if not convective:
+            self.theta_ext = 0.0
+
+    def ref(self, cs):
+        return BioheatBC(cs.pr, cs.k, cs.rho_c, cs.w, self.mask, self.rise, self.m_h, self.theta_ext)
+
+    def apply(self, th):
+        th.set_boundary(self.tags, fixed=self.fixed or None, convective=self.convective or None)
+
+
+@functools.lru_cache(maxsize=None)
+def standard(orc, label):
+    """The standard boundary of a case: x = lo fixed at the nodal rise 2 + sin(40 y); x = hi convective with h_c = 500 in
+    tissue cells and 200 in bone cells; y = lo convective with h_c = 300; theta_ext = -17 on both.  One edge sums two
+    convective faces, one edge decides fixed against convective; the remaining faces are insulating.  Returns
+    (Boundary, BioheatBC, rho_20 of the boundary operator)."""
+    cs = case(orc, label)
+    y = cs.prt.V.tabulate_dof_coordinates()[:, 1].astype(np.float64)
+    bone = materials(cs.prt.mesh, cs.hi)[0] == BONE["k"]
+    bd = Boundary(cs, {FIXED: (0, 0), CONV_X: (0, 1), CONV_Y: (1, 0)}, fixed={FIXED: 2.0 + np.sin(40.0 * y)},
+                  convective={CONV_X: (np.where(bone, 200.0, 500.0), THETA_EXT), CONV_Y: (300.0, THETA_EXT)})
+    ref = bd.ref(cs)
+    return bd, ref, ref.power_iteration(20)
+
+
+@functools.lru_cache(maxsize=None)
+def cooled_face(orc, label, h_c=5000.0):
+    """Forced water cooling on the face x = hi alone."""
+    cs = case(orc, label)
+    bd = Boundary(cs, {CONV_X: (0, 1)}, convective={CONV_X: (h_c, THETA_EXT)})
+    ref = bd.ref(cs)
+    return bd, ref, ref.power_iteration(20)
