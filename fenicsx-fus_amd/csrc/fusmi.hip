@@ -27,6 +27,7 @@
 #include "layout.hpp"
 #include "sts_coef.hpp"
 #include "thermal_bc.hpp"
+#include "thermal_owner.hpp"
 #include "tables.hpp"
 
 using namespace fus;
@@ -2099,7 +2100,42 @@ struct fus_thermal
   std::vector<void*> bc_allocs;   // the five lists of the boundary in force
   std::vector<void*> allocs;
   bool initialised = false;
+  // several ranks (fusmi.h "bioheat", several ranks): m_C, m_W, the heat weight and the fixed flags of the DOFs that other
+  // ranks hold too are ordered sums over the sharers.  Under RCCL the call that forms them exchanges at once; in an
+  // in-process group it leaves them `pending` for fus_group_thermal_finish.
+  enum { PEND_SETUP = 1, PEND_HEAT = 2, PEND_BC = 4 };
+  int pending = 0;
+  // pending heat load: this rank's part of M(q_coef) 1, and q -- a T vector, or the monitor's sum-of-squares plane in
+  // double with its sample count (qp_monitor) -- both n_internal long, allocated by the first call that needs them
+  void *mq = nullptr, *qp = nullptr;
+  bool qp_monitor = false;
+  double qp_nsamp = 1.0;
+  // the boundary as this rank's caller gave it last (caller numbering; an empty vector: NULL): the agreement over the
+  // sharers starts from it whenever any member of the group sets a boundary
+  std::vector<uint8_t> rq_fixed;
+  std::vector<char> rq_rise, rq_diag, rq_crise;
 };
+
+static bool thermal_multi(const fus_thermal* th) { return !th->op->neigh.empty(); }
+static bool thermal_in_group(const fus_thermal* th) { return thermal_multi(th) && th->ctx->local_group; }
+
+// vec(th) becomes the ordered sum over the sharers at the interface DOFs, the same bits on all of them: over RCCL for a
+// single object (nothing without neighbours), across the members of an in-process group otherwise
+static int thermal_sum(fus_thermal** ths, int n, void* (*vec)(fus_thermal*))
+{
+  if (n == 1 && !ths[0]->ctx->local_group)
+    return d_halo_sum(ths[0]->op, vec(ths[0]));
+  std::vector<fus_op*> ops(n);
+  for (int i = 0; i < n; ++i)
+  {
+    ops[i] = ths[i]->op;
+    FUSCHK(d_halo_pack(ops[i], vec(ths[i])));
+  }
+  FUSCHK(halo_exchange_local(ops.data(), n));
+  for (int i = 0; i < n; ++i)
+    FUSCHK(d_halo_unpack(ops[i], vec(ths[i])));
+  return FUS_OK;
+}
 
 // 1 / m_C as the stage and power kernels take it: zero at the fixed DOFs while there are any
 static const void* thermal_minv(const fus_thermal* th) { return th->nfix > 0 ? th->minv_bc : th->minv; }
@@ -2167,6 +2203,17 @@ static int thermal_lumped(fus_thermal* th, const T* coef_i, T* out)
   return FUS_OK;
 }
 
+// minv = 1 / m_C (0 in the padding slots), once m_C is complete
+template <typename T>
+static int thermal_setup_finish(fus_thermal* th)
+{
+  const int64_t n = th->op->L.n_internal;
+  hipLaunchKernelGGL((k_reciprocal<T>), dim3(nblk(n)), dim3(256), 0, th->ctx->stream, n, static_cast<const T*>(th->mc),
+                     static_cast<T*>(th->minv));
+  HIPCHK(hipGetLastError());
+  return FUS_OK;
+}
+
 template <typename T>
 static int thermal_setup(fus_thermal* th, const void* k_, const void* rc_, const void* w_)
 {
@@ -2194,13 +2241,21 @@ static int thermal_setup(fus_thermal* th, const void* k_, const void* rc_, const
   T* ci = static_cast<T*>(th->kneg);   // per-cell staging until -k takes it
   FUSCHK(thermal_cells_to_internal<T>(th, rc, ci));
   FUSCHK(thermal_lumped<T>(th, ci, static_cast<T*>(th->mc)));
-  hipLaunchKernelGGL((k_reciprocal<T>), dim3(nblk(n)), dim3(256), 0, st, n, static_cast<const T*>(th->mc),
-                     static_cast<T*>(th->minv));
+  // several ranks: 1 / m_C is formed from the sum over the sharers -- here over RCCL, in a group by fus_group_thermal_finish
+  const bool rccl = thermal_multi(th) && !th->ctx->local_group;
+  if (rccl)
+    FUSCHK(halo_sum<T>(op, static_cast<T*>(th->mc)));
+  if (!thermal_in_group(th))
+    FUSCHK(thermal_setup_finish<T>(th));
   if (wc)
   {
     FUSCHK(thermal_cells_to_internal<T>(th, wc, ci));
     FUSCHK(thermal_lumped<T>(th, ci, static_cast<T*>(th->mw)));
   }
+  if (rccl)   // collective: also where this rank has no perfusion
+    FUSCHK(halo_sum<T>(op, static_cast<T*>(th->mw)));
+  if (thermal_in_group(th))
+    th->pending |= fus_thermal::PEND_SETUP;
   std::vector<T> kn(nc);
   for (int64_t e = 0; e < nc; ++e)
     kn[e] = -kc[e];
@@ -2210,87 +2265,198 @@ static int thermal_setup(fus_thermal* th, const void* k_, const void* rc_, const
   return FUS_OK;
 }
 
+// grid and 16-byte vector count of a streaming pass over the whole vectors, or (local) over the DOFs no other rank holds:
+// [0, n_int_pad + n_if_start_pad), a multiple of 16 elements -- the interface DOFs behind it wait for the exchange
 template <typename T>
-static unsigned thermal_grid(const fus_thermal* th, int64_t* nvec)
+static unsigned thermal_grid(const fus_thermal* th, int64_t* nvec, bool local = false)
 {
-  *nvec = th->op->L.n_internal / (16 / (int64_t)sizeof(T));
+  const Layout& L = th->op->L;
+  *nvec = (local ? L.n_int_pad + L.n_if_start_pad : L.n_internal) / (16 / (int64_t)sizeof(T));
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((*nvec + 255) / 256, (int64_t)th->ctx->num_cus * 8));
 }
 
-// one classical RK4 step (a = 0, 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6): per stage the operator's two launches and
-// k_thermal_stage
+// First half of a stage of either scheme: b = K(-k) x, the convective term, and on several ranks the pack of this rank's
+// totals of the interface DOFs into the send buffer (the event hands it to the exchange)
 template <typename T>
-static int thermal_step(fus_thermal* th, double dt_, double sigma)
+static int thermal_stage_begin(fus_thermal* th, const T* x)
+{
+  FUSCHK(d_apply_int(th->op, OP_STIFFNESS, th->kneg, x, th->b));
+  FUSCHK(thermal_robin<T>(th, x, true));
+  if (thermal_multi(th))
+  {
+    ProfScope ps(th->ctx, "halo");
+    FUSCHK(halo_pack<T>(th->op, static_cast<const T*>(th->b)));
+  }
+  return FUS_OK;
+}
+
+// between the halves of a stage of a single object: the RCCL exchange on the comm stream (nothing without neighbours)
+static int thermal_exchange(fus_thermal* th)
+{
+  if (!thermal_multi(th))
+    return FUS_OK;
+  ProfScope ps(th->ctx, "halo");
+  return halo_exchange_rccl(th->op);
+}
+
+// classical RK4 (a = 0, 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6), stage i: per stage the operator's two launches and
+// k_thermal_stage; on several ranks that kernel covers the rank's own DOFs while the exchange is in flight, and
+// k_thermal_if_stage finishes the interface DOFs from the received totals
+template <typename T>
+static const T* thermal_rk4_input(const fus_thermal* th, int i)
+{
+  return static_cast<const T*>(i == 0 ? th->th0 : th->ths);
+}
+
+template <typename T>
+static int thermal_rk4_begin(fus_thermal* th, int i)
+{
+  return thermal_stage_begin<T>(th, thermal_rk4_input<T>(th, i));
+}
+
+template <typename T>
+static int thermal_rk4_end(fus_thermal* th, int i, double dt_, double sigma)
 {
   fus_op* op = th->op;
+  fus_ctx* c = th->ctx;
   const T dt = (T)dt_;
   const T a_next[4] = {T(0.5), T(0.5), T(1), T(0)};
   const T b_runge[4] = {(T)(1.0 / 6.0), (T)(1.0 / 3.0), (T)(1.0 / 3.0), (T)(1.0 / 6.0)};
+  const bool multi = thermal_multi(th);
   int64_t nvec;
-  const unsigned grid = thermal_grid<T>(th, &nvec);
-  for (int i = 0; i < 4; ++i)
+  const unsigned grid = thermal_grid<T>(th, &nvec, multi);
+  ThermalStage<T> A;
+  A.b = static_cast<const T*>(th->b), A.th_in = thermal_rk4_input<T>(th, i);
+  A.th_out = static_cast<T*>(i == 3 ? th->th0 : th->ths);
+  A.th0 = static_cast<const T*>(th->th0), A.acc = static_cast<T*>(th->acc);
+  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+  A.dose = th->dose;
+  A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
+  A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
   {
-    const T* x = static_cast<const T*>(i == 0 ? th->th0 : th->ths);
-    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, x, th->b));
-    FUSCHK(thermal_robin<T>(th, x, true));
-    ThermalStage<T> A;
-    A.b = static_cast<const T*>(th->b), A.th_in = x;
-    A.th_out = static_cast<T*>(i == 3 ? th->th0 : th->ths);
-    A.th0 = static_cast<const T*>(th->th0), A.acc = static_cast<T*>(th->acc);
-    A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
-    A.dose = th->dose;
-    A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
-    A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
-    ProfScope ps(th->ctx, "thermal");
+    ProfScope ps(c, "thermal");
     if (i == 0)
-      hipLaunchKernelGGL((k_thermal_stage<T, 0>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+      hipLaunchKernelGGL((k_thermal_stage<T, 0>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
     else if (i < 3)
-      hipLaunchKernelGGL((k_thermal_stage<T, 1>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+      hipLaunchKernelGGL((k_thermal_stage<T, 1>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
     else
-      hipLaunchKernelGGL((k_thermal_stage<T, 3>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+      hipLaunchKernelGGL((k_thermal_stage<T, 3>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
+    HIPCHK(hipGetLastError());
+  }
+  if (multi)
+  {
+    if (!c->local_group)
+      HIPCHK(hipStreamWaitEvent(c->stream, c->ev_recv, 0));
+    ProfScope ps(c, "thermal_if");
+    const dim3 gi(nblk(op->n_uidx)), blk(256);
+    const T* recv = static_cast<const T*>(op->d_recvbuf);
+    if (i == 0)
+      hipLaunchKernelGGL((k_thermal_if_stage<T, 0>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    else if (i < 3)
+      hipLaunchKernelGGL((k_thermal_if_stage<T, 1>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    else
+      hipLaunchKernelGGL((k_thermal_if_stage<T, 3>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
     HIPCHK(hipGetLastError());
   }
   return FUS_OK;
 }
 
-// one RKL2 step of c.s stages (sts_coef.hpp): per stage the operator's two launches and k_thermal_sts_stage.  Y_0 stays in
-// th0 until the last stage overwrites it, F_0 sits in f0, and Y_1, Y_2, ... alternate between ths and acc: Y_j lands
-// where Y_{j-2} was, except Y_2, whose Y_{j-2} is Y_0
+// one RK4 step of a single object: single rank, or RCCL
+template <typename T>
+static int thermal_step(fus_thermal* th, double dt_, double sigma)
+{
+  for (int i = 0; i < 4; ++i)
+  {
+    FUSCHK(thermal_rk4_begin<T>(th, i));
+    FUSCHK(thermal_exchange(th));
+    FUSCHK(thermal_rk4_end<T>(th, i, dt_, sigma));
+  }
+  return FUS_OK;
+}
+
+// RKL2 of c.s stages (sts_coef.hpp), stage j = 1..s: per stage the operator's two launches and k_thermal_sts_stage (on
+// several ranks split like an RK4 stage, k_thermal_if_sts_stage on the interface DOFs).  Y_0 stays in th0 until the last
+// stage overwrites it, F_0 sits in f0, and Y_1, Y_2, ... alternate between ths and acc: Y_j lands where Y_{j-2} was,
+// except Y_2, whose Y_{j-2} is Y_0
+template <typename T>
+static const T* thermal_sts_input(const fus_thermal* th, int j)
+{
+  return static_cast<const T*>(j == 1 ? th->th0 : ((j - 2) & 1 ? th->acc : th->ths));
+}
+
+template <typename T>
+static int thermal_sts_begin(fus_thermal* th, int j)
+{
+  return thermal_stage_begin<T>(th, thermal_sts_input<T>(th, j));
+}
+
+template <typename T>
+static int thermal_sts_end(fus_thermal* th, int j, double dt_, double sigma, const fus::StsCoef& c)
+{
+  fus_op* op = th->op;
+  fus_ctx* cx = th->ctx;
+  const bool multi = thermal_multi(th);
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec, multi);
+  T* rot[2] = {static_cast<T*>(th->ths), static_cast<T*>(th->acc)};
+  T* th0 = static_cast<T*>(th->th0);
+  ThermalSts<T> A;
+  A.b = static_cast<const T*>(th->b), A.y1 = thermal_sts_input<T>(th, j);
+  A.y2 = j <= 2 ? th0 : rot[(j - 1) & 1];
+  A.y0 = th0, A.f0 = static_cast<T*>(th->f0);
+  A.out = j == c.s ? th0 : rot[(j - 1) & 1];
+  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+  A.dose = th->dose;
+  A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
+  A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
+  A.dt120 = dt_ / 120.0, A.t_base = th->t_base;
+  {
+    ProfScope ps(cx, "thermal_sts");
+    if (j == 1)
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 0>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
+    else if (j < c.s)
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 1>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
+    else
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, 2>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
+    HIPCHK(hipGetLastError());
+  }
+  if (multi)
+  {
+    if (!cx->local_group)
+      HIPCHK(hipStreamWaitEvent(cx->stream, cx->ev_recv, 0));
+    ProfScope ps(cx, "thermal_if");
+    const dim3 gi(nblk(op->n_uidx)), blk(256);
+    const T* recv = static_cast<const T*>(op->d_recvbuf);
+    if (j == 1)
+      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 0>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    else if (j < c.s)
+      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 1>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    else
+      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 2>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    HIPCHK(hipGetLastError());
+  }
+  return FUS_OK;
+}
+
+// a fixed DOF passes through mu Y + nu Y + om Y in every stage, which returns Y only up to rounding (RK4's stages add
+// an exact zero instead): one sparse launch per step puts the values back, so that they hold exactly here too
+template <typename T>
+static int thermal_sts_finish(fus_thermal* th)
+{
+  return thermal_impose<T>(th, static_cast<T*>(th->th0));
+}
+
+// one RKL2 step of a single object: single rank, or RCCL
 template <typename T>
 static int thermal_step_sts(fus_thermal* th, double dt_, double sigma, const fus::StsCoef& c)
 {
-  fus_op* op = th->op;
-  int64_t nvec;
-  const unsigned grid = thermal_grid<T>(th, &nvec);
-  T* rot[2] = {static_cast<T*>(th->ths), static_cast<T*>(th->acc)};
-  T* th0 = static_cast<T*>(th->th0);
   for (int j = 1; j <= c.s; ++j)
   {
-    const T* y1 = j == 1 ? th0 : rot[(j - 2) & 1];
-    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, y1, th->b));
-    FUSCHK(thermal_robin<T>(th, y1, true));
-    ThermalSts<T> A;
-    A.b = static_cast<const T*>(th->b), A.y1 = y1;
-    A.y2 = j <= 2 ? th0 : rot[(j - 1) & 1];
-    A.y0 = th0, A.f0 = static_cast<T*>(th->f0);
-    A.out = j == c.s ? th0 : rot[(j - 1) & 1];
-    A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
-    A.dose = th->dose;
-    A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
-    A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
-    A.dt120 = dt_ / 120.0, A.t_base = th->t_base;
-    ProfScope ps(th->ctx, "thermal_sts");
-    if (j == 1)
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 0>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
-    else if (j < c.s)
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 1>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
-    else
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 2>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
-    HIPCHK(hipGetLastError());
+    FUSCHK(thermal_sts_begin<T>(th, j));
+    FUSCHK(thermal_exchange(th));
+    FUSCHK(thermal_sts_end<T>(th, j, dt_, sigma, c));
   }
-  // a fixed DOF passes through mu Y + nu Y + om Y in every stage, which returns Y only up to rounding (RK4's stages add
-  // an exact zero instead): one sparse launch per step puts the values back, so that they hold exactly here too
-  return thermal_impose<T>(th, th0);
+  return thermal_sts_finish<T>(th);
 }
 
 // h = M(qcoef_i) 1 .* q: q a T vector in internal numbering (q_i), or Q / nsamp from the monitor's plane (Q)
@@ -2298,15 +2464,50 @@ template <typename T>
 static int thermal_heat(fus_thermal* th, const T* qcoef_i, const T* q_i, const double* Q, double nsamp)
 {
   fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal;
   T* mq = static_cast<T*>(th->b);
   FUSCHK(thermal_lumped<T>(th, qcoef_i, mq));
+  if (thermal_in_group(th))
+  {
+    // the weight waits for the sharers' parts: keep it and q until fus_group_thermal_finish; h stays as it was
+    if (!th->mq)
+      FUSCHK(dalloc_bytes(th->allocs, &th->mq, n * sizeof(T), true, st));
+    if (!th->qp)
+      FUSCHK(dalloc_bytes(th->allocs, &th->qp, n * sizeof(double), true, st));
+    HIPCHK(hipMemcpyAsync(th->mq, mq, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if (q_i)
+      HIPCHK(hipMemcpyAsync(th->qp, q_i, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    else
+      HIPCHK(hipMemcpyAsync(th->qp, Q, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    th->qp_monitor = q_i == nullptr, th->qp_nsamp = nsamp;
+    th->pending |= fus_thermal::PEND_HEAT;
+  }
+  else
+  {
+    if (thermal_multi(th))
+      FUSCHK(halo_sum<T>(op, mq));
+    int64_t nvec;
+    const unsigned grid = thermal_grid<T>(th, &nvec);
+    hipLaunchKernelGGL((k_thermal_heat<T>), dim3(grid), dim3(256), 0, st, nvec, static_cast<const T*>(mq), q_i, Q, nsamp,
+                       static_cast<T*>(th->h));
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemsetAsync(th->b, 0, n * sizeof(T), st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+// the pending heat load of a group member, once its weight holds the sharers' parts
+template <typename T>
+static int thermal_heat_finish(fus_thermal* th)
+{
   int64_t nvec;
   const unsigned grid = thermal_grid<T>(th, &nvec);
-  hipLaunchKernelGGL((k_thermal_heat<T>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, static_cast<const T*>(mq), q_i, Q,
-                     nsamp, static_cast<T*>(th->h));
+  hipLaunchKernelGGL((k_thermal_heat<T>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, static_cast<const T*>(th->mq),
+                     th->qp_monitor ? nullptr : static_cast<const T*>(th->qp),
+                     th->qp_monitor ? static_cast<const double*>(th->qp) : nullptr, th->qp_nsamp, static_cast<T*>(th->h));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(th->b, 0, op->L.n_internal * sizeof(T), th->ctx->stream));
-  HIPCHK(hipStreamSynchronize(th->ctx->stream));
   return FUS_OK;
 }
 
@@ -2320,6 +2521,7 @@ static int thermal_set_heat(fus_thermal* th, const void* q, const void* q_coef, 
   {
     HIPCHK(hipMemsetAsync(th->h, 0, n * sizeof(T), st));
     HIPCHK(hipStreamSynchronize(st));
+    th->pending &= ~fus_thermal::PEND_HEAT;   // a load that waited for the sharers is dropped with it
     return FUS_OK;
   }
   T* cc = static_cast<T*>(op->d_tmp_coef);
@@ -2437,57 +2639,118 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
 // (the start vector is zero there, and so is every iterate: minv_bc).  Setup-time work: the operator and the quotient
 // y = (K(k) x + m_W x + m_H x) / m_C run on the device, y is pulled, the three m_C-weighted dot products and the normalisation
 // are done on the host in double, and the next x is pushed back.
+// Several ranks -- one object under RCCL, or the n members of an in-process group: every rank starts from its own
+// 1 + 0.5 sin(37 d + 1) over its own DOF numbers, one ordered sum makes the start the same on all sharers of a DOF, every
+// operator result is summed over the sharers, the dot products count a DOF on the rank that owns it (thermal_owner.hpp)
+// and their three sums are added over the ranks before the quotient is formed: every rank gets the same double.
 template <typename T>
-static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
+static int thermal_lambda_max(fus_thermal** ths, int n, int iters, double* lambda)
 {
-  fus_op* op = th->op;
-  hipStream_t st = th->ctx->stream;
-  const int64_t n = op->L.n_internal, nd = op->ndofs;
-  std::vector<T> xc(nd);
-  for (int64_t d = 0; d < nd; ++d)
-    xc[d] = (T)(1.0 + 0.5 * std::sin(37.0 * (double)d + 1.0));
-  T* tc = static_cast<T*>(op->d_tmp_c);
-  T* xd = static_cast<T*>(th->ths);   // the stage input's place is free between steps
-  T* yd = static_cast<T*>(th->acc);
-  HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(T), st));
-  HIPCHK(hipMemcpyAsync(tc, xc.data(), nd * sizeof(T), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, static_cast<const T*>(tc), xd);
-  HIPCHK(hipGetLastError());
-  FUSCHK(thermal_impose<T>(th, xd, true));
-  std::vector<T> x(n), y(n), mc(n);
-  HIPCHK(hipMemcpyAsync(x.data(), xd, n * sizeof(T), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mc.data(), th->mc, n * sizeof(T), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  struct Member
+  {
+    std::vector<T> x, y, mc;
+    std::vector<uint8_t> own;   // empty: every DOF is this rank's
+  };
+  std::vector<Member> M(n);
+  for (int i = 0; i < n; ++i)
+  {
+    fus_thermal* th = ths[i];
+    fus_op* op = th->op;
+    hipStream_t st = th->ctx->stream;
+    const int64_t ni = op->L.n_internal, nd = op->ndofs;
+    std::vector<T> xc(nd);
+    for (int64_t d = 0; d < nd; ++d)
+      xc[d] = (T)(1.0 + 0.5 * std::sin(37.0 * (double)d + 1.0));
+    T* tc = static_cast<T*>(op->d_tmp_c);
+    T* xd = static_cast<T*>(th->ths);   // the stage input's place is free between steps
+    HIPCHK(hipMemsetAsync(xd, 0, ni * sizeof(T), st));
+    HIPCHK(hipMemcpyAsync(tc, xc.data(), nd * sizeof(T), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, static_cast<const T*>(tc), xd);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // xc leaves scope
+    if (thermal_multi(th))
+    {
+      std::vector<int32_t> uidx(op->n_uidx), uptr(op->n_uidx + 1), usrc;
+      HIPCHK(hipMemcpy(uidx.data(), op->d_uidx, uidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(uptr.data(), op->d_uptr, uptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      usrc.resize((size_t)uptr.back());
+      HIPCHK(hipMemcpy(usrc.data(), op->d_usrc, usrc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (fus::thermal_owner_mask(ni, op->n_uidx, uidx.data(), uptr.data(), usrc.data(), &M[i].own) != fus::TOWN_OK)
+        return fail(FUS_ERR_STATE, "fus_thermal_lambda_max: malformed halo lists");
+    }
+  }
+  FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->ths; }));
+  for (int i = 0; i < n; ++i)
+  {
+    fus_thermal* th = ths[i];
+    hipStream_t st = th->ctx->stream;
+    const int64_t ni = th->op->L.n_internal;
+    FUSCHK(thermal_impose<T>(th, static_cast<T*>(th->ths), true));
+    M[i].x.resize(ni), M[i].y.resize(ni), M[i].mc.resize(ni);
+    HIPCHK(hipMemcpyAsync(M[i].x.data(), th->ths, ni * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(M[i].mc.data(), th->mc, ni * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
   double rho = 0.0;
   for (int it = 0; it < iters; ++it)
   {
-    FUSCHK(d_apply_int(op, OP_STIFFNESS, th->kneg, xd, th->b));
-    FUSCHK(thermal_robin<T>(th, xd, false));
-    hipLaunchKernelGGL((k_thermal_power<T>), dim3(1024), dim3(256), 0, st, n, static_cast<const T*>(th->b),
-                       static_cast<const T*>(xd), static_cast<const T*>(th->mw), static_cast<const T*>(thermal_minv(th)), yd);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(y.data(), yd, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    double xy = 0.0, xx = 0.0, yy = 0.0;
-    for (int64_t i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i)
     {
-      const double m = (double)mc[i], xi = (double)x[i], yi = (double)y[i];
-      xy += xi * (m * yi), xx += xi * (m * xi), yy += yi * (m * yi);
+      fus_thermal* th = ths[i];
+      FUSCHK(d_apply_int(th->op, OP_STIFFNESS, th->kneg, th->ths, th->b));
+      FUSCHK(thermal_robin<T>(th, static_cast<const T*>(th->ths), false));
     }
+    FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->b; }));
+    double dots[3] = {0.0, 0.0, 0.0};   // x . m y, x . m x, y . m y
+    for (int i = 0; i < n; ++i)
+    {
+      fus_thermal* th = ths[i];
+      hipStream_t st = th->ctx->stream;
+      const int64_t ni = th->op->L.n_internal;
+      Member& m = M[i];
+      hipLaunchKernelGGL((k_thermal_power<T>), dim3(1024), dim3(256), 0, st, ni, static_cast<const T*>(th->b),
+                         static_cast<const T*>(th->ths), static_cast<const T*>(th->mw),
+                         static_cast<const T*>(thermal_minv(th)), static_cast<T*>(th->acc));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(m.y.data(), th->acc, ni * sizeof(T), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      double xy = 0.0, xx = 0.0, yy = 0.0;
+      for (int64_t k = 0; k < ni; ++k)
+      {
+        if (!m.own.empty() && !m.own[k])
+          continue;
+        const double w = (double)m.mc[k], xi = (double)m.x[k], yi = (double)m.y[k];
+        xy += xi * (w * yi), xx += xi * (w * xi), yy += yi * (w * yi);
+      }
+      dots[0] += xy, dots[1] += xx, dots[2] += yy;
+    }
+    if (n == 1 && thermal_multi(ths[0]) && !ths[0]->ctx->local_group)
+      FUSCHK(fus_comm_allreduce(ths[0]->ctx, dots, 3, FUS_SUM));
+    const double xy = dots[0], xx = dots[1], yy = dots[2];
     if (!(xx > 0.0) || !std::isfinite(xy) || !std::isfinite(yy))
       return fail(FUS_ERR_STATE, "fus_thermal_lambda_max: the iteration broke down (zero or non-finite vector)");
     rho = xy / xx;
     if (!(yy > 0.0))   // k = 0 and W = 0 everywhere: the operator is zero
       break;
     const double nrm = std::sqrt(yy);
-    for (int64_t i = 0; i < n; ++i)
-      x[i] = (T)((double)y[i] / nrm);
-    HIPCHK(hipMemcpyAsync(xd, x.data(), n * sizeof(T), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i)
+    {
+      fus_thermal* th = ths[i];
+      Member& m = M[i];
+      for (size_t k = 0; k < m.x.size(); ++k)
+        m.x[k] = (T)((double)m.y[k] / nrm);
+      HIPCHK(hipMemcpyAsync(th->ths, m.x.data(), m.x.size() * sizeof(T), hipMemcpyHostToDevice, th->ctx->stream));
+      HIPCHK(hipStreamSynchronize(th->ctx->stream));
+    }
   }
-  HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(T), st));
-  HIPCHK(hipMemsetAsync(yd, 0, n * sizeof(T), st));
-  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i)
+  {
+    fus_thermal* th = ths[i];
+    const int64_t ni = th->op->L.n_internal;
+    HIPCHK(hipMemsetAsync(th->ths, 0, ni * sizeof(T), th->ctx->stream));
+    HIPCHK(hipMemsetAsync(th->acc, 0, ni * sizeof(T), th->ctx->stream));
+    HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  }
   *lambda = rho;
   return FUS_OK;
 }
@@ -2495,8 +2758,8 @@ static int thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
 // Replaces the boundary: the lists are built and validated on the host (thermal_bc.hpp), uploaded into buffers of their own
 // and only then put in force, so that an error leaves the previous boundary as it was.
 template <typename T>
-static int thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
-                                const void* conv_rise)
+static int thermal_install_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
+                                    const void* conv_rise)
 {
   fus_op* op = th->op;
   hipStream_t st = th->ctx->stream;
@@ -2544,6 +2807,100 @@ static int thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const voi
     HIPCHK(hipStreamSynchronize(st));
   }
   return FUS_OK;
+}
+
+// Several ranks: a DOF is fixed if any sharer fixes it, at the mean of the values the fixing sharers gave (callers are
+// expected to give the same one).  Ordered sums of the 0/1 flags and of flag * value make every sharer see the same
+// flags and values; the lists are then built from them, so a sharer drops its convective entry on a DOF another rank
+// fixed.  The convective diagonal is NOT summed: like the wave models' boundary weights each rank's part rides in its
+// partial b.  Every member starts from the boundary its caller gave last (rq_*), and installs the agreed one.
+template <typename T>
+static int thermal_agree_boundary(fus_thermal** ths, int n)
+{
+  for (int i = 0; i < n; ++i)
+  {
+    fus_thermal* th = ths[i];
+    fus_op* op = th->op;
+    hipStream_t st = th->ctx->stream;
+    const int64_t nd = op->ndofs;
+    const T* rise = th->rq_rise.empty() ? nullptr : reinterpret_cast<const T*>(th->rq_rise.data());
+    std::vector<T> flag(nd, T(0)), val(nd, T(0));
+    for (int64_t d = 0; d < nd; ++d)
+      if (!th->rq_fixed.empty() && th->rq_fixed[d])
+        flag[d] = T(1), val[d] = rise ? rise[d] : T(0);
+    T* tc = static_cast<T*>(op->d_tmp_c);
+    // flags and values in internal numbering: the stage input's and the accumulator's places are free between steps
+    for (int pass = 0; pass < 2; ++pass)
+    {
+      HIPCHK(hipMemcpyAsync(tc, (pass ? val : flag).data(), nd * sizeof(T), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL((k_to_internal<T>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, static_cast<const T*>(tc),
+                         static_cast<T*>(pass ? th->acc : th->ths));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+    }
+  }
+  FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->ths; }));
+  FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->acc; }));
+  int rc = FUS_OK;
+  for (int i = 0; i < n; ++i)
+  {
+    fus_thermal* th = ths[i];
+    fus_op* op = th->op;
+    hipStream_t st = th->ctx->stream;
+    const int64_t nd = op->ndofs, ni = op->L.n_internal;
+    std::vector<T> cnt(nd), sum(nd);
+    T* tc = static_cast<T*>(op->d_tmp_c);
+    for (int pass = 0; pass < 2; ++pass)
+    {
+      hipLaunchKernelGGL((k_from_internal<T, 0>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm,
+                         static_cast<const T*>(pass ? th->acc : th->ths), tc);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync((pass ? sum : cnt).data(), tc, nd * sizeof(T), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipMemsetAsync(th->ths, 0, ni * sizeof(T), st));
+    HIPCHK(hipMemsetAsync(th->acc, 0, ni * sizeof(T), st));
+    std::vector<uint8_t> fixed(nd);
+    std::vector<T> rise(nd, T(0));
+    for (int64_t d = 0; d < nd; ++d)
+      if ((fixed[d] = cnt[d] > T(0.5)))
+        rise[d] = (T)((double)sum[d] / (double)cnt[d]);
+    const int r = thermal_install_boundary<T>(th, fixed.data(), rise.data(), th->rq_diag.empty() ? nullptr : th->rq_diag.data(),
+                                              th->rq_crise.empty() ? nullptr : th->rq_crise.data());
+    if (r == FUS_OK)
+      th->pending &= ~fus_thermal::PEND_BC;
+    else if (rc == FUS_OK)   // every member still takes part in what follows; the first error is reported
+      rc = r;
+  }
+  return rc;
+}
+
+template <typename T>
+static int thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
+                                const void* conv_rise)
+{
+  if (!thermal_multi(th))
+    return thermal_install_boundary<T>(th, fixed, fixed_rise, conv_diag, conv_rise);
+  // validated before anything is kept: an error leaves the previous boundary, and the previous request, as they were
+  fus::ThermalBcLists<T> L;
+  const int err = fus::thermal_bc_lists<T>(th->op->ndofs, th->op->L.dof_perm.data(), fixed, static_cast<const T*>(fixed_rise),
+                                           static_cast<const T*>(conv_diag), static_cast<const T*>(conv_rise), &L);
+  if (err != fus::TBC_OK)
+    return fail(FUS_ERR_ARG, std::string("fus_thermal_set_boundary: ") + fus::thermal_bc_message(err));
+  const size_t nd = (size_t)th->op->ndofs;
+  auto keep = [nd](std::vector<char>& v, const void* a)
+  {
+    const char* q = static_cast<const char*>(a);
+    v.assign(q, q + (a ? nd * sizeof(T) : 0));
+  };
+  th->rq_fixed.assign(fixed, fixed + (fixed ? nd : 0));
+  keep(th->rq_rise, fixed_rise), keep(th->rq_diag, conv_diag), keep(th->rq_crise, conv_rise);
+  if (thermal_in_group(th))
+  {
+    th->pending |= fus_thermal::PEND_BC;
+    return FUS_OK;
+  }
+  return thermal_agree_boundary<T>(&th, 1);
 }
 
 // ---- phased / apodised source (fusmi.h) ----
@@ -3773,6 +4130,64 @@ int fus_model_monitor_get(fus_model* m, int quantity, int k, void* out, int spac
 // ---- bioheat (fusmi.h): the typed implementation sits with the monitor's, ahead of the C ABI ----
 #define FUS_TH_CALL(th, fn, ...) ((th)->op->dtype == FUS_F64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
+// FUS_ERR_STATE while sums over the sharers wait for fus_group_thermal_finish
+static int thermal_ready(const fus_thermal* th, const char* fn)
+{
+  if (th->pending)
+    return fail(FUS_ERR_STATE, std::string(fn) + ": sums over the sharers of the interface DOFs are pending; "
+                                                 "fus_group_thermal_finish must be called first");
+  return FUS_OK;
+}
+
+// the single-object calls that exchange: not on a member of an in-process group
+static int thermal_single(const fus_thermal* th, const char* fn, const char* group_fn)
+{
+  FUSCHK(thermal_ready(th, fn));
+  if (thermal_in_group(th))
+    return fail(FUS_ERR_STATE, std::string(fn) + ": in-process transport: use " + group_fn);
+  return FUS_OK;
+}
+
+// the members of a group call: objects of one scalar type on one device, in in-process contexts of distinct ranks, every
+// neighbour of every member among them
+static int thermal_group(fus_thermal** ths, int n, const char* fn)
+{
+  if (!ths || n < 1)
+    return fail(FUS_ERR_ARG, std::string(fn) + ": bad group");
+  for (int i = 0; i < n; ++i)
+  {
+    if (!ths[i])
+      return fail(FUS_ERR_ARG, std::string(fn) + ": null member");
+    if (ths[i]->op->dtype != ths[0]->op->dtype || ths[i]->ctx->device != ths[0]->ctx->device)
+      return fail(FUS_ERR_ARG, std::string(fn) + ": the members differ in scalar type or device");
+    if (thermal_multi(ths[i]) && !ths[i]->ctx->local_group)
+      return fail(FUS_ERR_ARG, std::string(fn) + ": a member's context is not part of an in-process group (fus_comm_init_local)");
+    for (int j = 0; j < i; ++j)
+      if (ths[j] == ths[i] || ths[j]->ctx->rank == ths[i]->ctx->rank)
+        return fail(FUS_ERR_ARG, std::string(fn) + ": two members of one rank");
+  }
+  for (int i = 0; i < n; ++i)
+    for (const Neigh& nb : ths[i]->op->neigh)
+    {
+      bool found = false;
+      for (int j = 0; j < n; ++j)
+        found = found || ths[j]->ctx->rank == nb.rank;
+      if (!found)
+        return fail(FUS_ERR_ARG, std::string(fn) + ": the group lacks rank " + std::to_string(nb.rank) + ", a neighbour of rank "
+                                     + std::to_string(ths[i]->ctx->rank));
+    }
+  return FUS_OK;
+}
+
+static int thermal_step_args(const char* fn, double dt, int64_t nsteps, double heat_scale)
+{
+  if (!(dt > 0) || !std::isfinite(dt))
+    return fail(FUS_ERR_ARG, std::string(fn) + ": dt must be positive and finite");
+  if (nsteps < 0 || !std::isfinite(heat_scale))
+    return fail(FUS_ERR_ARG, std::string(fn) + ": nsteps must be >= 0 and heat_scale finite");
+  return FUS_OK;
+}
+
 int fus_thermal_create(fus_ctx* c, fus_op* op, const void* conductivity, const void* rho_c, const void* perfusion,
                        double t_base, fus_thermal** out)
 {
@@ -3782,9 +4197,10 @@ int fus_thermal_create(fus_ctx* c, fus_op* op, const void* conductivity, const v
     return fail(FUS_ERR_ARG, "fus_thermal_create: the operator data belongs to another context");
   if (!std::isfinite(t_base))
     return fail(FUS_ERR_ARG, "fus_thermal_create: t_base must be finite");
-  if (!op->neigh.empty() || c->nranks > 1)
-    return fail(FUS_ERR_STATE, "fus_thermal_create: several ranks are not supported (the operator action inside the "
-                               "thermal step does no inter-rank reduction)");
+  if ((!op->neigh.empty() || c->nranks > 1) && !(c->comm || (c->local_group && !c->external_transport)))
+    return fail(FUS_ERR_STATE, "fus_thermal_create: several ranks need a transport of the library's own: an RCCL communicator "
+                               "(fus_comm_init) or an in-process group (fus_comm_init_local); the external-transport entry "
+                               "points do not cover the thermal model");
   HIPCHK(hipSetDevice(c->device));
   std::unique_ptr<fus_thermal> th(new fus_thermal());
   th->ctx = c, th->op = op, th->t_base = t_base;
@@ -3817,6 +4233,7 @@ int fus_thermal_init(fus_thermal* th)
 {
   if (!th)
     return fail(FUS_ERR_ARG, "fus_thermal_init: null argument");
+  FUSCHK(thermal_ready(th, "fus_thermal_init"));
   HIPCHK(hipSetDevice(th->ctx->device));
   const int64_t n = th->op->L.n_internal;
   for (void* v : {th->th0, th->ths, th->acc})
@@ -3832,6 +4249,7 @@ int fus_thermal_set(fus_thermal* th, int which, const void* in, int space)
 {
   if (!th || !in || (which != FUS_TH_RISE && which != FUS_TH_DOSE) || (space != FUS_HOST && space != FUS_DEVICE))
     return fail(FUS_ERR_ARG, "fus_thermal_set: null argument, which not FUS_TH_RISE | FUS_TH_DOSE, or bad space");
+  FUSCHK(thermal_ready(th, "fus_thermal_set"));
   HIPCHK(hipSetDevice(th->ctx->device));
   FUSCHK(FUS_TH_CALL(th, thermal_vec, th, which, const_cast<void*>(in), space, true));
   th->initialised = true;
@@ -3876,18 +4294,17 @@ int fus_thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
     return fail(FUS_ERR_ARG, "fus_thermal_lambda_max: null argument");
   if (iters < 1)
     return fail(FUS_ERR_ARG, "fus_thermal_lambda_max: iters must be at least 1");
+  FUSCHK(thermal_single(th, "fus_thermal_lambda_max", "fus_group_thermal_lambda_max"));
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_lambda_max, th, iters, lambda);
+  return FUS_TH_CALL(th, thermal_lambda_max, &th, 1, iters, lambda);
 }
 
 int fus_thermal_steps(fus_thermal* th, double dt, int64_t nsteps, double heat_scale)
 {
   if (!th)
     return fail(FUS_ERR_ARG, "fus_thermal_steps: null argument");
-  if (!(dt > 0) || !std::isfinite(dt))
-    return fail(FUS_ERR_ARG, "fus_thermal_steps: dt must be positive and finite");
-  if (nsteps < 0 || !std::isfinite(heat_scale))
-    return fail(FUS_ERR_ARG, "fus_thermal_steps: nsteps must be >= 0 and heat_scale finite");
+  FUSCHK(thermal_step_args("fus_thermal_steps", dt, nsteps, heat_scale));
+  FUSCHK(thermal_single(th, "fus_thermal_steps", "fus_group_thermal_steps"));
   if (!th->initialised)
     return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called before fus_thermal_steps");
   HIPCHK(hipSetDevice(th->ctx->device));
@@ -3904,10 +4321,8 @@ int fus_thermal_steps_sts(fus_thermal* th, double dt, int64_t nsteps, double hea
   fus::StsCoef coef;
   if (!fus::sts_coefficients(stages, &coef))
     return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: stages must lie in 2..32");
-  if (!(dt > 0) || !std::isfinite(dt))
-    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: dt must be positive and finite");
-  if (nsteps < 0 || !std::isfinite(heat_scale))
-    return fail(FUS_ERR_ARG, "fus_thermal_steps_sts: nsteps must be >= 0 and heat_scale finite");
+  FUSCHK(thermal_step_args("fus_thermal_steps_sts", dt, nsteps, heat_scale));
+  FUSCHK(thermal_single(th, "fus_thermal_steps_sts", "fus_group_thermal_steps"));
   if (!th->initialised)
     return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called before fus_thermal_steps_sts");
   HIPCHK(hipSetDevice(th->ctx->device));
@@ -3917,6 +4332,124 @@ int fus_thermal_steps_sts(fus_thermal* th, double dt, int64_t nsteps, double hea
     FUSCHK(FUS_TH_CALL(th, thermal_step_sts, th, dt, heat_scale, coef));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
   return FUS_OK;
+}
+
+// ---- bioheat on the members of an in-process group (fusmi.h "bioheat", several ranks) ----
+int fus_group_thermal_finish(fus_thermal** ths, int n)
+{
+  FUSCHK(thermal_group(ths, n, "fus_group_thermal_finish"));
+  int any = 0, all = ~0;
+  for (int i = 0; i < n; ++i)
+    any |= ths[i]->pending, all &= ths[i]->pending;
+  if ((any & ~all) & fus_thermal::PEND_SETUP)
+    return fail(FUS_ERR_STATE, "fus_group_thermal_finish: some members have been finished before and some have not; create the "
+                               "thermal objects of all ranks, then finish them together");
+  if ((any & ~all) & fus_thermal::PEND_HEAT)
+    return fail(FUS_ERR_STATE, "fus_group_thermal_finish: a heat load waits on some members only; fus_thermal_set_heat / "
+                               "fus_thermal_set_heat_from_monitor must be called on every member");
+  HIPCHK(hipSetDevice(ths[0]->ctx->device));
+  if (any & fus_thermal::PEND_SETUP)
+  {
+    FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->mc; }));
+    FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->mw; }));
+    for (int i = 0; i < n; ++i)
+    {
+      FUSCHK(FUS_TH_CALL(ths[i], thermal_setup_finish, ths[i]));
+      ths[i]->pending &= ~fus_thermal::PEND_SETUP;
+    }
+  }
+  if (any & fus_thermal::PEND_BC)   // one member's new boundary may fix DOFs of the others: all agree again
+    FUSCHK(FUS_TH_CALL(ths[0], thermal_agree_boundary, ths, n));
+  if (any & fus_thermal::PEND_HEAT)
+  {
+    FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->mq; }));
+    for (int i = 0; i < n; ++i)
+    {
+      FUSCHK(FUS_TH_CALL(ths[i], thermal_heat_finish, ths[i]));
+      ths[i]->pending &= ~fus_thermal::PEND_HEAT;
+    }
+  }
+  for (int i = 0; i < n; ++i)
+    HIPCHK(hipStreamSynchronize(ths[i]->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_group_thermal_steps(fus_thermal** ths, int n, double dt, int64_t nsteps, double heat_scale, int stages)
+{
+  FUSCHK(thermal_group(ths, n, "fus_group_thermal_steps"));
+  fus::StsCoef coef;
+  if (stages != 0 && !fus::sts_coefficients(stages, &coef))
+    return fail(FUS_ERR_ARG, "fus_group_thermal_steps: stages must be 0 (RK4) or lie in 2..32");
+  FUSCHK(thermal_step_args("fus_group_thermal_steps", dt, nsteps, heat_scale));
+  for (int i = 0; i < n; ++i)
+  {
+    FUSCHK(thermal_ready(ths[i], "fus_group_thermal_steps"));
+    if (!ths[i]->initialised)
+      return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called on every member before fus_group_thermal_steps");
+  }
+  HIPCHK(hipSetDevice(ths[0]->ctx->device));
+  std::vector<fus_op*> ops(n);
+  for (int i = 0; i < n; ++i)
+  {
+    ops[i] = ths[i]->op;
+    if (stages != 0 && !ths[i]->f0)
+      FUSCHK(dalloc_bytes(ths[i]->allocs, &ths[i]->f0, ops[i]->L.n_internal * ops[i]->ts, true, ths[i]->ctx->stream));
+  }
+  // as fus_group_rk4_steps: the first halves of all members (they end with the pack), the exchange, the second halves
+  for (int64_t s = 0; s < nsteps; ++s)
+  {
+    for (int st = 0; st < (stages == 0 ? 4 : stages); ++st)
+    {
+      for (int i = 0; i < n; ++i)
+        FUSCHK(stages == 0 ? FUS_TH_CALL(ths[i], thermal_rk4_begin, ths[i], st) : FUS_TH_CALL(ths[i], thermal_sts_begin, ths[i], st + 1));
+      FUSCHK(halo_exchange_local(ops.data(), n));
+      for (int i = 0; i < n; ++i)
+        FUSCHK(stages == 0 ? FUS_TH_CALL(ths[i], thermal_rk4_end, ths[i], st, dt, heat_scale)
+                           : FUS_TH_CALL(ths[i], thermal_sts_end, ths[i], st + 1, dt, heat_scale, coef));
+    }
+    if (stages != 0)
+      for (int i = 0; i < n; ++i)
+        FUSCHK(FUS_TH_CALL(ths[i], thermal_sts_finish, ths[i]));
+  }
+  for (int i = 0; i < n; ++i)
+    HIPCHK(hipStreamSynchronize(ths[i]->ctx->stream));
+  return FUS_OK;
+}
+
+static int thermal_group_lambda(fus_thermal** ths, int n, int iters, const char* fn, double* lambda)
+{
+  FUSCHK(thermal_group(ths, n, fn));
+  if (!lambda)
+    return fail(FUS_ERR_ARG, std::string(fn) + ": null argument");
+  if (iters < 1)
+    return fail(FUS_ERR_ARG, std::string(fn) + ": iters must be at least 1");
+  for (int i = 0; i < n; ++i)
+    FUSCHK(thermal_ready(ths[i], fn));
+  HIPCHK(hipSetDevice(ths[0]->ctx->device));
+  return FUS_TH_CALL(ths[0], thermal_lambda_max, ths, n, iters, lambda);
+}
+
+int fus_group_thermal_lambda_max(fus_thermal** ths, int n, int iters, double* lambda)
+{
+  return thermal_group_lambda(ths, n, iters, "fus_group_thermal_lambda_max", lambda);
+}
+
+// lambda_max turned into a step: 2 / rho for RK4 (stages = 0), 0.72 beta_s / rho for RKL2
+static int thermal_dt_from(const char* fn, double rho, int stages, double* dt)
+{
+  if (!(rho > 0.0))
+    return fail(FUS_ERR_STATE, std::string(fn) + ": the operator is zero (k = 0 and W = 0 everywhere): any step is stable");
+  *dt = stages == 0 ? 2.0 / rho : 0.72 * fus::sts_beta(stages) / rho;
+  return FUS_OK;
+}
+
+int fus_group_thermal_stable_dt(fus_thermal** ths, int n, int iters, int stages, double* dt)
+{
+  if (stages != 0 && !fus::sts_stages_ok(stages))
+    return fail(FUS_ERR_ARG, "fus_group_thermal_stable_dt: stages must be 0 (RK4) or lie in 2..32");
+  double rho = 0.0;
+  FUSCHK(thermal_group_lambda(ths, n, iters, "fus_group_thermal_stable_dt", dt ? &rho : nullptr));
+  return thermal_dt_from("fus_group_thermal_stable_dt", rho, stages, dt);
 }
 
 int fus_thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* fixed_rise, const void* conv_diag,
@@ -3947,13 +4480,11 @@ int fus_thermal_stable_dt(fus_thermal* th, int iters, int stages, double* dt)
     return fail(FUS_ERR_ARG, "fus_thermal_stable_dt: iters must be at least 1");
   if (stages != 0 && !fus::sts_stages_ok(stages))
     return fail(FUS_ERR_ARG, "fus_thermal_stable_dt: stages must be 0 (RK4) or lie in 2..32");
+  FUSCHK(thermal_single(th, "fus_thermal_stable_dt", "fus_group_thermal_stable_dt"));
   HIPCHK(hipSetDevice(th->ctx->device));
   double rho = 0.0;
-  FUSCHK(FUS_TH_CALL(th, thermal_lambda_max, th, iters, &rho));
-  if (!(rho > 0.0))
-    return fail(FUS_ERR_STATE, "fus_thermal_stable_dt: the operator is zero (k = 0 and W = 0 everywhere): any step is stable");
-  *dt = stages == 0 ? 2.0 / rho : 0.72 * fus::sts_beta(stages) / rho;
-  return FUS_OK;
+  FUSCHK(FUS_TH_CALL(th, thermal_lambda_max, &th, 1, iters, &rho));
+  return thermal_dt_from("fus_thermal_stable_dt", rho, stages, dt);
 }
 
 int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nsteps)

@@ -3878,6 +3878,86 @@ k_thermal_fix(int64_t nf, const int32_t* __restrict__ idx, const T* __restrict__
     minv_bc[i] = T(0);
 }
 
+// ---- the bioheat model on several ranks: interface DOFs (fusmi.h "bioheat", several ranks) ----
+// The streaming stage kernels above then stop at the first interface slot; the DOFs that other ranks hold too are
+// finished here, after the exchange, in the form of k_if_unpack_stage: one thread per entry j of uidx, the ordered sum
+// over usrc[uptr[j] .. uptr[j + 1]) of the rank's own total b[u] (-1) and the sharers' totals in the receive buffer
+// (ascending rank order: the same bits on every sharer), then the stage update of that one DOF with the formulas, the
+// argument structs and the dose functions of the streaming kernels.  Every other operand is identical on all sharers
+// (m_C, m_W and the heat weight are ordered sums themselves, the state starts identical), so the results are too.
+// uidx is ascending and mostly contiguous: neighbouring lanes hit neighbouring addresses.  No LDS, no atomics; a
+// thread reads every value of its DOF before it writes one, so th_out / out may alias the inputs as they do above.
+template <typename T>
+__device__ __forceinline__ T thermal_if_sum(int64_t j, T own, const int32_t* __restrict__ uptr,
+                                            const int32_t* __restrict__ usrc, const T* __restrict__ recvbuf)
+{
+  T acc = T(0);
+  for (int32_t k = uptr[j]; k < uptr[j + 1]; ++k)
+  {
+    const int32_t sidx = usrc[k];
+    acc += (sidx < 0) ? own : recvbuf[sidx];
+  }
+  return acc;
+}
+
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256)
+k_thermal_if_stage(int64_t nu, const int32_t* __restrict__ uidx, const int32_t* __restrict__ uptr,
+                   const int32_t* __restrict__ usrc, const T* __restrict__ recvbuf, const ThermalStage<T> A)
+{
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nu)
+    return;
+  const int64_t u = uidx[j];
+  const T b = thermal_if_sum<T>(j, A.b[u], uptr, usrc, recvbuf);
+  const T th = A.th_in[u];
+  const T k = (b - A.mw[u] * th + A.sigma * A.h[u]) * A.minv[u];
+  if (STAGE == 0)
+  {
+    A.acc[u] = th + A.bdt * k;
+    A.th_out[u] = th + A.adt * k;
+  }
+  else if (STAGE == 1)
+  {
+    const T t0 = A.th0[u], a = A.acc[u];
+    A.acc[u] = a + A.bdt * k;
+    A.th_out[u] = t0 + A.adt * k;
+  }
+  else
+  {
+    const T tn = A.acc[u] + A.bdt * k;
+    A.th_out[u] = tn;
+    A.dose[u] = thermal_dose_add(A.dose[u], (double)tn, A.t_base, A.dt60);
+  }
+}
+
+template <typename T, int KIND>
+__global__ void __launch_bounds__(256)
+k_thermal_if_sts_stage(int64_t nu, const int32_t* __restrict__ uidx, const int32_t* __restrict__ uptr,
+                       const int32_t* __restrict__ usrc, const T* __restrict__ recvbuf, const ThermalSts<T> A)
+{
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nu)
+    return;
+  const int64_t u = uidx[j];
+  const T b = thermal_if_sum<T>(j, A.b[u], uptr, usrc, recvbuf);
+  const T y1 = A.y1[u];
+  const T f = (b - A.mw[u] * y1 + A.sigma * A.h[u]) * A.minv[u];
+  if (KIND == 0)
+  {
+    A.f0[u] = f;
+    A.out[u] = y1 + A.mdt * f;
+  }
+  else
+  {
+    const T y2 = A.y2[u], y0 = A.y0[u], f0 = A.f0[u];
+    const T yn = A.mu * y1 + A.nu * y2 + A.om * y0 + A.mdt * f + A.gdt * f0;
+    A.out[u] = yn;
+    if (KIND == 2)
+      A.dose[u] = thermal_dose_add_trapezoid(A.dose[u], (double)y0, (double)yn, A.t_base, A.dt120);
+  }
+}
+
 // halo helpers
 // pack: sendbuf[k] = vec[idx[k]] over the concatenated neighbour lists
 // Receiver sampling (the reference evaluates its solution at points with Function::eval after locating their cells:

@@ -10,5 +10,6 @@ from .models import (LinearSpectralExplicit, LossySpectralExplicit, WesterveltSp
                      group_finish_setup, group_rk4_steps)
 from .operators import (MassSpectral2D, MassSpectral3D, SpectralOperatorData, StiffnessSpectral2D,  # noqa: F401
                         StiffnessSpectral3D)
-from .thermal import BioheatSpectralExplicit  # noqa: F401,E402
+from .thermal import (BioheatSpectralExplicit, group_thermal_finish, group_thermal_lambda_max,  # noqa: F401,E402
+                      group_thermal_stable_dt, group_thermal_steps)
 from .unstructured import HexFunctionSpace, HexMesh, QuadMesh, read_xdmf_hex_mesh, read_xdmf_mesh  # noqa: F401,E402

@@ -77,7 +77,10 @@ class BioheatSpectralExplicit:
     None = 0) one value per cell; ``t_base`` the arterial and initial temperature in degrees C.  ``model=`` shares the
     operator data of a wave model (required for :meth:`set_heat_from`), ``data=`` an existing
     :class:`SpectralOperatorData` (as the operator classes take it); the object then does not own the data and
-    :meth:`close` leaves it alone.  Several ranks are not supported."""
+    :meth:`close` leaves it alone.  On a mesh part with neighbours (``V.neighbours``) the context needs a transport:
+    under an RCCL communicator the calls of this class are collective; the members of an in-process group are finished
+    and advanced together by :func:`group_thermal_finish`, :func:`group_thermal_steps`, :func:`group_thermal_lambda_max`
+    and :func:`group_thermal_stable_dt`."""
 
     def __init__(self, mesh, k, conductivity, rho_c, perfusion=None, t_base: float = 37.0, V=None,
                  ctx: Context | None = None, model=None, data: SpectralOperatorData | None = None):
@@ -276,3 +279,36 @@ class BioheatSpectralExplicit:
             self.h = C.c_void_p()
         if self._own_data:
             self.data.close()
+
+
+def _handles(bios):
+    return (C.c_void_p * len(bios))(*[b.h for b in bios]), C.c_int(len(bios))
+
+
+def group_thermal_finish(bios):
+    """In-process transport: the sharers' parts of m_C, m_W, the heat weight and the boundary flags of every member are
+    added (ordered sums, the same bits on all sharers).  Call it after the members are created and again after any
+    ``set_heat`` / ``set_heat_from`` / ``set_boundary``; a call with nothing pending does nothing."""
+    check(lib().fus_group_thermal_finish(*_handles(bios)))
+
+
+def group_thermal_steps(bios, dt: float, nsteps: int, heat_scale: float = 1.0, stages: int = 0):
+    """In-process transport: ``nsteps`` steps of all members in lock-step, RK4 (``stages`` = 0) or RKL2 (2..32)."""
+    arr, n = _handles(bios)
+    check(lib().fus_group_thermal_steps(arr, n, C.c_double(dt), C.c_int64(nsteps), C.c_double(heat_scale), C.c_int(stages)))
+
+
+def group_thermal_lambda_max(bios, iters: int = 20) -> float:
+    """:meth:`BioheatSpectralExplicit.lambda_max` of the operator the members hold together."""
+    arr, n = _handles(bios)
+    out = C.c_double()
+    check(lib().fus_group_thermal_lambda_max(arr, n, C.c_int(iters), C.byref(out)))
+    return out.value
+
+
+def group_thermal_stable_dt(bios, stages: int = 0, iters: int = 20) -> float:
+    """:meth:`BioheatSpectralExplicit.stable_dt` of the operator the members hold together."""
+    arr, n = _handles(bios)
+    out = C.c_double()
+    check(lib().fus_group_thermal_stable_dt(arr, n, C.c_int(iters), C.c_int(stages), C.byref(out)))
+    return out.value

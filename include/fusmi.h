@@ -443,8 +443,44 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  * another fus_op than the thermal object's.  FUS_ERR_STATE:
  * steps before fus_thermal_init / fus_thermal_set; fus_thermal_stable_dt on a zero operator (k = 0 and W = 0 everywhere:
  * every step is stable); fus_thermal_set_heat_from_monitor while the model's monitor is off,
- * has no sample, or watches FUS_V; an op on which fus_op_set_neighbours was called -- SEVERAL RANKS ARE OUT OF SCOPE:
- * the operator action inside a thermal step does no inter-rank reduction. */
+ * has no sample, or watches FUS_V; an op on which fus_op_set_neighbours was called in a context without a transport
+ * (below); a call that needs sums which still wait for fus_group_thermal_finish; a single-object call that exchanges, on
+ * a member of an in-process group.
+ * Several ranks: fus_thermal_create accepts an op with neighbours when the context has a transport of the library's own,
+ * an RCCL communicator (fus_comm_init) or an in-process group (fus_comm_init_local).  Without one -- a plain context, or
+ * one set up for the external transport, whose entry points do not cover the thermal model -- it fails with FUS_ERR_STATE
+ * before anything is allocated.  An interface DOF (one that other ranks hold too) then works as in the wave models: every
+ * rank forms its own total, the totals are exchanged, and every sharer adds them in ascending rank order, so that all
+ * of them hold the same bits.
+ *   Setup sums.  m_C, m_W and the heat weight M(q_coef) 1 are such sums, formed before their first use: 1 / m_C after
+ *   the sum of m_C, h = (M(q_coef) 1) .* q after the sum of the weight.  The convective diagonal m_H and r are NOT summed:
+ *   like the wave models' boundary weights each rank's part rides in its partial operator result.  A DOF is fixed if any
+ *   sharer fixes it, at the mean of the values the fixing sharers gave (callers are expected to give the same one): sums
+ *   of the 0/1 flags and of flag * value; a sharer drops its convective entry on a DOF another rank fixed.
+ *   Under RCCL fus_thermal_create, fus_thermal_set_heat (q != NULL), fus_thermal_set_heat_from_monitor and
+ *   fus_thermal_set_boundary are collective and exchange at once.  In an in-process group they leave the sums pending, and
+ *   fus_group_thermal_finish performs whatever is pending on the members: idempotent, and legal again after a later
+ *   set_heat or set_boundary (a new boundary on one member makes all members agree again; a heat load must be set on
+ *   all members or none).  While something is pending fus_thermal_init, _set, _steps, _steps_sts, _lambda_max and
+ *   _stable_dt fail with FUS_ERR_STATE.
+ *   The step.  Each stage is split as the wave models' stages are.  First half: the operator's two launches and the
+ *   convective term leave this rank's total in b, also at the interface DOFs; these are packed into the send buffer
+ *   (profile name "halo").  Second half: the streaming kernel runs over the DOFs no other rank holds -- the first
+ *   n_int_pad + n_if_start_pad slots, a multiple of 16 -- while the exchange is in flight, and after the receive one
+ *   thread per interface DOF adds the totals in order and applies the same stage update, dose included (profile name
+ *   "thermal_if").  Under RCCL fus_thermal_steps / _steps_sts do this as collective calls; the members of an in-process
+ *   group are advanced in lock-step by fus_group_thermal_steps (stages = 0: RK4; 2..32: RKL2), which checks arguments
+ *   and states of every member before anything is enqueued; the single-object calls fail there with FUS_ERR_STATE.
+ *   Without neighbours a step enqueues exactly the launches of the one-rank path, with the same arguments.
+ *   Step rule.  Every rank starts from 1 + 0.5 sin(37 d + 1) over its OWN DOF numbers; one ordered sum makes the start
+ *   identical on the sharers of a DOF (an interface DOF carries the sum of its sharers' values), the fixed DOFs are
+ *   zeroed.  Every operator result is exchanged; the three inner products count a DOF on the rank that owns it -- the
+ *   lowest rank that holds it -- and are added over the ranks (ncclAllReduce, or on the host across the group) before the
+ *   quotient is formed, so every rank gets the same double.  fus_group_thermal_lambda_max / _stable_dt for a group.
+ *   One fus_op serves EITHER thermal steps OR wave steps at a time: both use its send / receive buffers and d_partial
+ *   (for d_partial this was the rule already); calls in turns on the context's stream are fine, concurrent ones are not.
+ *   Not covered: the external transport, graph capture of thermal steps, overlapping the exchange with part of the block
+ *   kernel ("overlap_blocks" has no effect here). */
 typedef struct fus_thermal fus_thermal;
 enum { FUS_TH_RISE = 0, FUS_TH_DOSE = 1, FUS_TH_HEAT = 2 };
 int fus_thermal_create(fus_ctx* ctx, fus_op* op, const void* conductivity, const void* rho_c,
@@ -465,6 +501,12 @@ int fus_thermal_set_boundary(fus_thermal* thermal, const uint8_t* fixed /* [ndof
                              const void* fixed_rise /* T[ndofs], read where fixed */,
                              const void* conv_diag /* T[ndofs] = m_H >= 0 */, const void* conv_rise /* T[ndofs] */);
 int fus_thermal_boundary_info(fus_thermal* thermal, int64_t* nfixed, int64_t* nconvective);
+/* the members of an in-process group, one thermal object per rank, in any order */
+int fus_group_thermal_finish(fus_thermal** thermals, int n);
+int fus_group_thermal_steps(fus_thermal** thermals, int n, double dt, int64_t nsteps, double heat_scale,
+                            int stages /* 0: RK4; 2..32: RKL2 */);
+int fus_group_thermal_lambda_max(fus_thermal** thermals, int n, int iters, double* lambda);
+int fus_group_thermal_stable_dt(fus_thermal** thermals, int n, int iters, int stages, double* dt);
 
 int fus_group_finish_setup(fus_model** models, int n);
 int fus_group_rk4_steps(fus_model** models, int n, double t0, double dt, int64_t nsteps);
@@ -499,7 +541,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
  * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform),
  * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared"), "thermal_sts" (the
  * same for a super-time-stepping stage), "thermal_bc" (convective surface term, once per operator application of a
- * bioheat object with convective DOFs), "thermal_fix" (writes of the fixed values).  total_ms/count accumulate since the last enable.
+ * bioheat object with convective DOFs), "thermal_fix" (writes of the fixed values), "thermal_if" (bioheat stage update of
+ * the interface DOFs on several ranks; the pack of their totals counts under "halo").  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

@@ -363,7 +363,9 @@ public:
 // Pennes bioheat model and CEM43 dose on the operator's mesh (fusmi.h "bioheat"; the reference has no thermal model):
 //   rho C dtheta/dt = div(k grad theta) - W theta + Q for the temperature RISE theta over t_base, classical RK4 or,
 //   with stages = s in 2..32, the super-time-stepping scheme RKL2 (s operator applications per step, trapezoid dose).
-// conductivity, rho_c, perfusion (nullptr = 0): one value per cell.  One rank only.
+// conductivity, rho_c, perfusion (nullptr = 0): one value per cell.  On operator data with neighbours the context needs an
+// RCCL communicator (comm_init), and the constructor, set_heat, set_heat_from, set_boundary, steps, lambda_max and stable_dt
+// are collective calls; the members of an in-process group are driven through the C calls fus_group_thermal_* instead.
 template <typename T, int P>
 class BioheatSpectral3D
 {
