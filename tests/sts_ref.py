@@ -58,21 +58,24 @@ def polynomial(s, z):
 
 
 def step(bio, theta, dt, s, h=None, sigma=1.0):
-    """One RKL2 step of thermal_ref.Bioheat ``bio``."""
+    """One RKL2 step of thermal_ref.Bioheat ``bio``, in its scalar type T.  In float the stage scalars are rounded as
+    thermal_sts_end (fusmi.hip) rounds them: mu_j, nu_j, 1 - mu_j - nu_j, mut_j dt and gat_j dt are each formed in
+    double and rounded to T once; in double the rounding changes nothing."""
     mu, nu, mut, gat = coefficients(s)
+    T = bio.T
     y0 = theta
     f0 = bio.f(y0, h, sigma)
-    ym2, ym1 = y0, y0 + mut[1] * dt * f0
+    ym2, ym1 = y0, y0 + T(mut[1] * dt) * f0
     for j in range(2, s + 1):
-        y = (mu[j] * ym1 + nu[j] * ym2 + (1.0 - mu[j] - nu[j]) * y0 + mut[j] * dt * bio.f(ym1, h, sigma)
-             + gat[j] * dt * f0)
+        y = (T(mu[j]) * ym1 + T(nu[j]) * ym2 + T(1.0 - mu[j] - nu[j]) * y0 + T(mut[j] * dt) * bio.f(ym1, h, sigma)
+             + T(gat[j] * dt) * f0)
         ym2, ym1 = ym1, y
-    return ym1
+    return bio.finish_step(ym1)
 
 
 def run(bio, theta0, dt, nsteps, s, h=None, sigma=1.0, keep=False):
     """theta after ``nsteps`` steps; with ``keep`` the list of the states after every step."""
-    th, states = np.array(theta0, dtype=np.float64), []
+    th, states = bio.vec(theta0), []
     for _ in range(nsteps):
         th = step(bio, th, dt, s, h, sigma)
         if keep:

@@ -8,7 +8,10 @@ cell coefficient h_c) and r = m_H .* theta_ext,
 r is not scaled by sigma; a DOF both fixed and convective is fixed.  The power iteration runs on
 m_C^-1 (K(k) + diag(m_W + m_H)) with the rows and columns of the fixed DOFs removed.  ``BioheatBC`` overrides ``f``,
 ``start_vector`` and ``power_iteration`` only, so ``Bioheat.run`` and ``sts_ref.step`` / ``run`` work on it unchanged from
-a start that carries the fixed values (``impose``).  Also the standard boundary the device tests share."""
+a start that carries the fixed values (``impose``).  On a float Problem it is the float restatement of what the library
+computes (thermal_ref.Bioheat): the stage is Bioheat's with the hooks ``b`` (the convective term joins K(-k) theta as
+k_thermal_robin adds it), ``minv`` (zero at the fixed DOFs) and ``finish_step`` (the fixed values put back after a step).
+Also the standard boundary the device tests share."""
 import functools
 
 import numpy as np
@@ -28,21 +31,37 @@ class BioheatBC(Bioheat):
     def __init__(self, pr, k, rho_c, w=None, fixed=None, fixed_rise=None, m_h=None, theta_ext=None):
         super().__init__(pr, k, rho_c, w)
         n = pr.ndofs
-        full = lambda a: np.broadcast_to(np.asarray(0.0 if a is None else a, dtype=np.float64), (n,)).copy()   # noqa: E731
+        full = lambda a: np.broadcast_to(np.asarray(0.0 if a is None else a, dtype=pr.dtype), (n,)).copy()   # noqa: E731
+        zero = self.T(0)
         self.fixed = np.zeros(n, bool) if fixed is None else np.asarray(fixed).astype(bool)
-        self.fixed_rise = np.where(self.fixed, full(fixed_rise), 0.0)
-        self.m_h = np.where(self.fixed, 0.0, full(m_h))
+        self.fixed_rise = np.where(self.fixed, full(fixed_rise), zero)
+        self.m_h = np.where(self.fixed, zero, full(m_h))
         self.r = self.m_h * full(theta_ext)
         assert (self.m_h >= 0).all()
 
     def impose(self, theta):
-        return np.where(self.fixed, self.fixed_rise, np.asarray(theta, dtype=np.float64))
+        return np.where(self.fixed, self.fixed_rise, self.vec(theta))
+
+    def minv(self):
+        """Zero at the fixed DOFs, as the copy of 1 / m_C that k_thermal_fix prepares."""
+        return np.where(self.fixed, self.T(0), super().minv())
+
+    def b(self, theta):
+        """Float: the convective term joins the operator's result as k_thermal_robin adds it, b += r - m_H theta."""
+        return super().b(theta) + (self.r - self.m_h * theta)
 
     def f(self, theta, h=None, sigma=1.0):
+        if not self.exact:
+            return super().f(theta, h, sigma)
         r = self.pr.K(theta, -self.k) - self.m_w * theta - self.m_h * theta + self.r
         if h is not None and sigma != 0.0:
             r = r + sigma * h
         return np.where(self.fixed, 0.0, r / self.m_c)
+
+    def finish_step(self, theta):
+        """Float: the library puts the fixed values back after every step (thermal_sts_finish: mu Y + nu Y + om Y
+        returns Y only up to rounding; RK4's stages add an exact zero there)."""
+        return theta if self.exact else self.impose(theta)
 
     def start_vector(self):
         return np.where(self.fixed, 0.0, super().start_vector())
@@ -110,17 +129,27 @@ class Boundary:
             self.fixed[tag] = temp
             self.mask |= on
             self.rise[on] = (temp - T_BASE).astype(t).astype(np.float64)[on]    # as set_boundary forms and rounds it
-        self.m_h = np.zeros(n)
+        self.m_h, m_h_t = np.zeros(n), np.zeros(n)
         for tag, (h_c, ext) in (convective or {}).items():
             hc = np.broadcast_to(np.asarray(h_c, dtype=np.float64), (pr.mesh.num_cells,)).copy()
             self.convective[tag] = (hc.astype(t), T_BASE + ext)
             self.m_h += pr.facet_diag(self.tags, tag, hc)
+            if t != np.float64:      # as set_boundary forms it: every face's diagonal in T, their sum in double
+                m_h_t += cs.prt.facet_diag(self.tags, tag, hc.astype(t)).astype(np.float64)
             self.theta_ext = float(ext)                                          # one coolant per boundary
+        self.m_h_t = m_h_t.astype(t)                                             # ... and rounded to T once
         if not convective:
             self.theta_ext = 0.0
 
     def ref(self, cs):
         return BioheatBC(cs.pr, cs.k, cs.rho_c, cs.w, self.mask, self.rise, self.m_h, self.theta_ext)
+
+    def ref_t(self, cs, k=None, h_c_scale=1.0):
+        """The float restatement on the case's own float problem (``k``: another conductivity; ``h_c_scale``: m_H
+        scaled, the negative controls of test_thermal_fp32_guards.py)."""
+        assert cs.dtype == np.float32
+        m_h = (self.m_h_t.astype(np.float64) * h_c_scale).astype(cs.dtype)
+        return BioheatBC(cs.prt, cs.k if k is None else k, cs.rho_c, cs.w, self.mask, self.rise, m_h, self.theta_ext)
 
     def apply(self, th):
         th.set_boundary(self.tags, fixed=self.fixed or None, convective=self.convective or None)

@@ -4,7 +4,9 @@
     dtheta/dt = f(theta) = (K(-k) theta - m_W .* theta + sigma h) ./ m_C
 
 advanced by classical RK4 (a = 0, 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6, as in source_ref.py), the CEM43 dose rule and
-the power iteration behind the stable step, plus the materials, the heat field and the cases the tests share."""
+the power iteration behind the stable step, plus the materials, the heat field and the cases the tests share.  The model
+runs in the scalar type of the Problem it is given: in double it is the reference, in float the yardstick of the fp32
+budget tests (thermal_fp32_cases.py)."""
 import functools
 
 import numpy as np
@@ -63,40 +65,66 @@ def dose(states, dt, t_base):
 
 
 class Bioheat:
-    """The discrete Pennes model on a double Problem ``pr`` with per-cell k, rho_c, W (arrays or scalars)."""
+    """The discrete Pennes model on a Problem ``pr`` with per-cell k, rho_c, W (arrays or scalars), in ``pr``'s scalar
+    type T.  In double it is the reference.  In float it is the plain sequential restatement of what the library computes
+    (the yardstick of fp32_budget.py): K and M are the float oracle's, every vector is float32, and every scalar is
+    rounded where fusmi.hip rounds it -- dt to T first and then times T(a), T(b) (thermal_rk4_end), sigma to T, and the
+    stage multiplies by the stored vector 1 / m_C (k_reciprocal) where the double reference divides by m_C."""
 
     def __init__(self, pr, k, rho_c, w=None):
-        assert pr.dtype == np.float64
         nc = pr.mesh.num_cells
-        full = lambda a: np.broadcast_to(np.asarray(a, dtype=np.float64), (nc,)).copy()   # noqa: E731
+        self.T = pr.dtype.type
+        self.exact = pr.dtype == np.float64
+        full = lambda a: np.broadcast_to(np.asarray(a, dtype=pr.dtype), (nc,)).copy()   # noqa: E731
         self.pr, self.k, self.rho_c = pr, full(k), full(rho_c)
         self.w = full(0.0 if w is None else w)
-        one = np.ones(pr.ndofs)
+        one = np.ones(pr.ndofs, pr.dtype)
         self.m_c = pr.M(one, self.rho_c)
-        self.m_w = pr.M(one, self.w) if self.w.any() else np.zeros(pr.ndofs)
+        self.m_w = pr.M(one, self.w) if self.w.any() else np.zeros(pr.ndofs, pr.dtype)
+
+    def vec(self, a):
+        return np.array(a, dtype=self.pr.dtype)
 
     def load(self, q, coef=None):
         """h = (M(coef) 1) .* q"""
-        return self.pr.M(np.ones(self.pr.ndofs), None if coef is None else np.asarray(coef, dtype=np.float64)) * q
+        one = np.ones(self.pr.ndofs, self.pr.dtype)
+        return self.pr.M(one, None if coef is None else np.asarray(coef, dtype=self.pr.dtype)) * self.vec(q)
+
+    def minv(self):
+        """1 / m_C as the float stage kernels read it: a stored T vector."""
+        return self.T(1) / self.m_c
+
+    def b(self, theta):
+        """K(-k) theta: the operator's part of a stage."""
+        return self.pr.K(theta, -self.k)
 
     def f(self, theta, h=None, sigma=1.0):
-        r = self.pr.K(theta, -self.k) - self.m_w * theta
+        if not self.exact:
+            hh = np.zeros_like(theta) if h is None else h
+            assert theta.dtype == hh.dtype == self.pr.dtype
+            return (self.b(theta) - self.m_w * theta + self.T(sigma) * hh) * self.minv()
+        r = self.b(theta) - self.m_w * theta
         if h is not None and sigma != 0.0:
             r = r + sigma * h
         return r / self.m_c
 
+    def finish_step(self, theta):
+        """What a stepper does to the state after its last stage (the boundary reference's hook)."""
+        return theta
+
     def step(self, theta, dt, h=None, sigma=1.0):
         acc, stage = theta.copy(), theta
+        dt = self.T(dt)
         for i in range(4):
             ki = self.f(stage, h, sigma)
-            acc = acc + dt * B_RK[i] * ki
+            acc = acc + dt * self.T(B_RK[i]) * ki
             if i < 3:
-                stage = theta + dt * A_RK[i + 1] * ki
-        return acc
+                stage = theta + dt * self.T(A_RK[i + 1]) * ki
+        return self.finish_step(acc)
 
     def run(self, theta0, dt, nsteps, h=None, sigma=1.0, keep=False):
         """theta after ``nsteps`` steps; with ``keep`` the list of the states after every step."""
-        th, states = np.array(theta0, dtype=np.float64), []
+        th, states = self.vec(theta0), []
         for _ in range(nsteps):
             th = self.step(th, dt, h, sigma)
             if keep:
