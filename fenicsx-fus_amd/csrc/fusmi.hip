@@ -2110,6 +2110,9 @@ struct fus_thermal
   void *mq = nullptr, *qp = nullptr;
   bool qp_monitor = false;
   double qp_nsamp = 1.0;
+  // the pending mq is this rank's part of the per-harmonic load itself (fus_thermal_set_heat_from_harmonics): the sum over
+  // the sharers is then the load, and qp was only the scratch plane of the sum over the harmonics
+  bool pend_load = false;
   // the boundary as this rank's caller gave it last (caller numbering; an empty vector: NULL): the agreement over the
   // sharers starts from it whenever any member of the group sets a boundary
   std::vector<uint8_t> rq_fixed;
@@ -2480,7 +2483,7 @@ static int thermal_heat(fus_thermal* th, const T* qcoef_i, const T* q_i, const d
       HIPCHK(hipMemcpyAsync(th->qp, q_i, n * sizeof(T), hipMemcpyDeviceToDevice, st));
     else
       HIPCHK(hipMemcpyAsync(th->qp, Q, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    th->qp_monitor = q_i == nullptr, th->qp_nsamp = nsamp;
+    th->qp_monitor = q_i == nullptr, th->qp_nsamp = nsamp, th->pend_load = false;
     th->pending |= fus_thermal::PEND_HEAT;
   }
   else
@@ -2502,6 +2505,11 @@ static int thermal_heat(fus_thermal* th, const T* qcoef_i, const T* q_i, const d
 template <typename T>
 static int thermal_heat_finish(fus_thermal* th)
 {
+  if (th->pend_load)   // per-harmonic load: the sharers' parts of h itself have been summed
+  {
+    HIPCHK(hipMemcpyAsync(th->h, th->mq, th->op->L.n_internal * sizeof(T), hipMemcpyDeviceToDevice, th->ctx->stream));
+    return FUS_OK;
+  }
   int64_t nvec;
   const unsigned grid = thermal_grid<T>(th, &nvec);
   hipLaunchKernelGGL((k_thermal_heat<T>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, static_cast<const T*>(th->mq),
@@ -2575,6 +2583,59 @@ static int thermal_heat_from_monitor(fus_thermal* th, fus_model* m, const void* 
   HIPCHK(hipGetLastError());
   const double* Q = reinterpret_cast<const double*>(static_cast<const T*>(m->d_mon) + 2 * n) + n;   // acc plane 1
   return thermal_heat<T>(th, cc, nullptr, Q, (double)m->mon_n);
+}
+
+// h = sum_k M(2 alpha_k / (rho c)) 1 .* (2 / n^2) (C_k^2 + S_k^2) over the harmonics 1..nharm of the model's monitor
+// (fusmi.h "bioheat", per-harmonic heat load): per harmonic the lumped weight into b and one launch of
+// k_thermal_heat_harmonic, which carries the sum in the double plane qp.  Several ranks: the sharers' parts of h are
+// summed -- at once over RCCL, by fus_group_thermal_finish in a group, where the part waits in mq.
+template <typename T>
+static int thermal_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm, const void* absorption)
+{
+  fus_op* op = th->op;
+  hipStream_t st = th->ctx->stream;
+  const int64_t n = op->L.n_internal, nc = op->ncells;
+  const T* al = static_cast<const T*>(absorption);
+  for (int64_t e = 0; e < (int64_t)nharm * nc; ++e)
+    if (!(al[e] >= T(0)) || !std::isfinite((double)al[e]))
+      return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: absorption must be >= 0 and finite in every cell and row");
+  const bool group = thermal_in_group(th);
+  if (nharm > 1 && !th->qp)
+    FUSCHK(dalloc_bytes(th->allocs, &th->qp, n * sizeof(double), true, st));
+  if (group && !th->mq)
+    FUSCHK(dalloc_bytes(th->allocs, &th->mq, n * sizeof(T), true, st));
+  T* cc = static_cast<T*>(op->d_tmp_coef);
+  T* ci = cc + nc;
+  T* mk = static_cast<T*>(th->b);
+  T* out = static_cast<T*>(group ? th->mq : th->h);   // in a group h stays as it was until the finish
+  const double* acc = reinterpret_cast<const double*>(static_cast<const T*>(m->d_mon) + 2 * n);
+  const double ns = (double)m->mon_n;
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec);
+  for (int k = 1; k <= nharm; ++k)
+  {
+    HIPCHK(hipMemcpyAsync(cc, al + (int64_t)(k - 1) * nc, nc * sizeof(T), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((k_cells_to_internal<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, op->d_cell_perm,
+                       static_cast<const T*>(cc), ci);
+    hipLaunchKernelGGL((k_thermal_qcoef<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, static_cast<const T*>(ci),
+                       static_cast<const T*>(m->d_rho0), static_cast<const T*>(m->d_c0), cc);
+    HIPCHK(hipGetLastError());
+    FUSCHK(thermal_lumped<T>(th, cc, mk));
+    hipLaunchKernelGGL((k_thermal_heat_harmonic<T>), dim3(grid), dim3(256), 0, st, nvec, static_cast<const T*>(mk),
+                       acc + (size_t)(1 + k) * n, acc + (size_t)(1 + m->mon_nharm + k) * n, static_cast<double*>(th->qp),
+                       k == 1 ? 1 : 0, k == nharm ? 2.0 / (ns * ns) : 0.0, out);
+    HIPCHK(hipGetLastError());
+  }
+  if (group)
+  {
+    th->pend_load = true;
+    th->pending |= fus_thermal::PEND_HEAT;
+  }
+  else if (thermal_multi(th))
+    FUSCHK(halo_sum<T>(op, out));
+  HIPCHK(hipMemsetAsync(th->b, 0, n * sizeof(T), st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
 }
 
 template <typename T>
@@ -4288,6 +4349,26 @@ int fus_thermal_set_heat_from_monitor(fus_thermal* th, fus_model* m, const void*
   return FUS_TH_CALL(th, thermal_heat_from_monitor, th, m, absorption);
 }
 
+int fus_thermal_set_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm, const void* absorption)
+{
+  if (!th || !m || !absorption)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: null argument");
+  if (m->op != th->op)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: the model runs on another fus_op than the thermal object");
+  if (nharm < 1 || nharm > 8)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: nharm must lie in 1..8");
+  if (m->mon_every <= 0 || !m->d_mon)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the model's monitor is off (fus_model_monitor)");
+  if (m->mon_which != FUS_U)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor watches FUS_V; the heat needs the pressure, FUS_U");
+  if (m->mon_n == 0)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor has taken no sample yet");
+  if (nharm > m->mon_nharm)
+    return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor holds fewer harmonics than nharm asks for");
+  HIPCHK(hipSetDevice(th->ctx->device));
+  return FUS_TH_CALL(th, thermal_heat_from_harmonics, th, m, nharm, absorption);
+}
+
 int fus_thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
 {
   if (!th || !lambda)
@@ -4347,6 +4428,11 @@ int fus_group_thermal_finish(fus_thermal** ths, int n)
   if ((any & ~all) & fus_thermal::PEND_HEAT)
     return fail(FUS_ERR_STATE, "fus_group_thermal_finish: a heat load waits on some members only; fus_thermal_set_heat / "
                                "fus_thermal_set_heat_from_monitor must be called on every member");
+  if (all & fus_thermal::PEND_HEAT)
+    for (int i = 1; i < n; ++i)
+      if (ths[i]->pend_load != ths[0]->pend_load)
+        return fail(FUS_ERR_STATE, "fus_group_thermal_finish: the heat loads that wait on the members are of different kinds; "
+                                   "call fus_thermal_set_heat_from_harmonics on every member or on none");
   HIPCHK(hipSetDevice(ths[0]->ctx->device));
   if (any & fus_thermal::PEND_SETUP)
   {

@@ -3820,6 +3820,47 @@ k_thermal_heat(int64_t nvec, const T* __restrict__ mq, const T* __restrict__ q, 
   }
 }
 
+// Per-harmonic heat load (fus_thermal_set_heat_from_harmonics), one launch per harmonic k in ascending order:
+//   sum += (double) m_k .* (C_k^2 + S_k^2),   m_k = M(2 alpha_k / (rho c)) 1,
+// C_k, S_k the field monitor's cosine / sine planes of harmonic k (k_monitor_accumulate).  The running sum lives in one
+// double plane: `first` starts it (the plane is not read), every launch but the last stores it back, and the last one
+// (scale != 0) forms sum * scale, scale = 2 / nsamp^2, rounds to T once and stores h -- so the fp32 error does not grow
+// with the number of harmonics.  A single harmonic (first and last) touches no sum plane at all.  Streaming like
+// k_thermal_heat: 16-byte accesses, grid-stride over nvec, no LDS, no atomics.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_thermal_heat_harmonic(int64_t nvec, const T* __restrict__ mk, const double* __restrict__ Ck, const double* __restrict__ Sk,
+                        double* __restrict__ sum, int first, double scale, T* __restrict__ h)
+{
+#pragma clang fp contract(off)
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV m = __builtin_nontemporal_load(reinterpret_cast<const TV*>(mk) + i);
+    TV out;
+#pragma unroll
+    for (int j = 0; j < VEC / 2; ++j)
+    {
+      const int64_t at = i * VEC + 2 * j;
+      const D2 c = __builtin_nontemporal_load(reinterpret_cast<const D2*>(Ck + at));
+      const D2 s = __builtin_nontemporal_load(reinterpret_cast<const D2*>(Sk + at));
+      D2 a;
+      a[0] = (double)m[2 * j] * (c[0] * c[0] + s[0] * s[0]);
+      a[1] = (double)m[2 * j + 1] * (c[1] * c[1] + s[1] * s[1]);
+      if (!first)
+        a = __builtin_nontemporal_load(reinterpret_cast<const D2*>(sum + at)) + a;
+      if (scale != 0.0)
+        out[2 * j] = (T)(a[0] * scale), out[2 * j + 1] = (T)(a[1] * scale);
+      else
+        __builtin_nontemporal_store(a, reinterpret_cast<D2*>(sum + at));
+    }
+    if (scale != 0.0)
+      __builtin_nontemporal_store(out, reinterpret_cast<TV*>(h) + i);
+  }
+}
+
 // q_coef = 2 alpha / (rho c) per cell, internal cell order (alpha: amplitude absorption, Np/m)
 template <typename T>
 __global__ void k_thermal_qcoef(int64_t n, const T* __restrict__ alpha, const T* __restrict__ rho, const T* __restrict__ c,

@@ -32,7 +32,8 @@ SYMBOLS = [
     "fus_model_monitor", "fus_model_monitor_get", "fus_model_monitor_info",
     "fus_model_set_source",
     "fus_thermal_create", "fus_thermal_destroy", "fus_thermal_init", "fus_thermal_set", "fus_thermal_get",
-    "fus_thermal_set_heat", "fus_thermal_set_heat_from_monitor", "fus_thermal_lambda_max", "fus_thermal_steps",
+    "fus_thermal_set_heat", "fus_thermal_set_heat_from_monitor", "fus_thermal_set_heat_from_harmonics",
+    "fus_thermal_lambda_max", "fus_thermal_steps",
     "fus_thermal_steps_sts", "fus_thermal_stable_dt", "fus_thermal_set_boundary", "fus_thermal_boundary_info",
     "fus_group_thermal_finish", "fus_group_thermal_steps", "fus_group_thermal_lambda_max", "fus_group_thermal_stable_dt",
 ]

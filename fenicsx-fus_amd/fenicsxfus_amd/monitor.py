@@ -60,3 +60,25 @@ def whole_period_window(freq, dt_max, t_end, nperiods, every=1, nharm=0):
     if skip < 0:
         raise ValueError(f"{nperiods} periods ({nperiods * spp} steps) do not fit into the {nsteps} steps to t_end")
     return dt, nsteps, skip, spp
+
+
+def power_law(alpha, y, nharm):
+    """Absorption of the harmonics ``1..nharm`` under the power law ``alpha(f) ~ f^y``: an array of shape
+    ``(nharm, ncells)`` whose row ``k - 1`` is ``alpha * k**y``.  ``alpha``: amplitude absorption in Np/m at the source
+    frequency, one value per cell (or a scalar: one column); ``y``: a scalar or one value per cell (about 1 to 1.3 in
+    soft tissue, 2 in water and thermoviscous media).  What ``BioheatSpectralExplicit.set_heat_from`` takes as a 2-D
+    ``absorption``."""
+    if int(nharm) < 1:
+        raise ValueError("nharm >= 1")
+    alpha, y = np.atleast_1d(_arr(alpha)), _arr(y)
+    k = np.arange(1, int(nharm) + 1, dtype=np.float64)[:, None]
+    return alpha[None, :] * k ** np.broadcast_to(y, alpha.shape)[None, :]
+
+
+def thermoviscous_absorption(delta, c, f):
+    """``delta (2 pi f)^2 / (2 c^3)``: the amplitude absorption in Np/m at the frequency ``f`` that the Lossy and
+    Westervelt models themselves impose through the diffusivity of sound ``delta`` (the inverse of
+    ``compute_diffusivity_of_sound``, which takes the attenuation in dB/m = Np/m * 20 / ln 10).  It grows like f^2, so ``power_law(thermoviscous_absorption(delta, c, f0), 2, K)``
+    makes the heat load equal what the wave loses."""
+    delta, c = _arr(delta), _arr(c)
+    return delta * (2.0 * np.pi * f) ** 2 / (2.0 * c ** 3)

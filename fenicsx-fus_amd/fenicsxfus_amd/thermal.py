@@ -8,7 +8,8 @@ with classical RK4 on the GPU, or with the super-time-stepping scheme RKL2 (``st
 applications per step, a step about ``(s^2 + s - 2) / 5.6`` times the RK4 step), and accumulates the thermal dose in
 cumulative equivalent minutes at 43 degrees C.  The
 heat load comes from a nodal field (:meth:`set_heat`) or, without leaving the device, from the field monitor of a wave
-model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``.  Every face is
+model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``, or harmonic by harmonic
+with an absorption that grows with frequency.  Every face is
 insulating until :meth:`BioheatSpectralExplicit.set_boundary` holds it at a temperature (a cut face in tissue) or lets it
 exchange heat with a coolant (water-cooled skin).  The reference package has no thermal model; this module replaces
 nothing there."""
@@ -151,7 +152,22 @@ class BioheatSpectralExplicit:
     def set_heat_from(self, model, absorption):
         """Acoustic heating ``Q = 2 alpha p_rms^2 / (rho c)`` from the field monitor of ``model`` (watching u, at least
         one sample), on the device: ``absorption`` = alpha, amplitude absorption in Np/m at the source frequency, one
-        value per cell (or a scalar).  ``model`` must be the one this object was created with (``model=``)."""
+        value per cell (or a scalar).  ``model`` must be the one this object was created with (``model=``).
+
+        A 2-D ``absorption`` of shape ``(K, ncells)`` takes the per-harmonic load instead (fusmi.h "per-harmonic heat
+        load"): row ``k - 1`` is alpha at ``k`` times the source frequency (:func:`fenicsxfus_amd.monitor.power_law`),
+        and ``Q = sum_k 2 alpha_k <p_k^2> / (rho c)`` over the harmonics ``1..K`` of the monitor (``nharm >= K``),
+        ``<p_k^2>`` the mean square of harmonic ``k`` over the monitor's window -- whole periods, see
+        :func:`fenicsxfus_amd.monitor.whole_period_window`.  The mean and the harmonics above ``K`` carry no heat."""
+        if np.ndim(_array(absorption)) == 2:
+            a = np.ascontiguousarray(_array(absorption), dtype=self.dtype)
+            if a.shape[1] == 1:                                   # one value for all cells, as a scalar alpha gives
+                a = np.ascontiguousarray(np.broadcast_to(a, (a.shape[0], self.data.ncells)))
+            if a.shape[1] != self.data.ncells:
+                raise _abi.FusError(f"absorption: expected {self.data.ncells} values per harmonic, one per cell, got shape "
+                                    f"{a.shape}")
+            check(lib().fus_thermal_set_heat_from_harmonics(self.h, model.h, C.c_int(a.shape[0]), ptr(a)))
+            return
         a = self._cells(absorption, "absorption")
         check(lib().fus_thermal_set_heat_from_monitor(self.h, model.h, ptr(a)))
 

@@ -427,6 +427,8 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  *                        the device: q = Q / n from the monitor's sum-of-squares plane and sample count, formed in
  *                        double (the RMS map is never rounded through a square root), q_coef = 2 alpha / (rho c) with
  *                        the model's rho0 and c0; absorption = alpha, host T[ncells], >= 0.  The monitor keeps sampling
+ *   fus_thermal_set_heat_from_harmonics   h from the monitor's harmonics, each with its own absorption ("per-harmonic
+ *                        heat load" below); preconditions and errors as fus_thermal_set_heat_from_monitor
  *   fus_thermal_steps    nsteps RK4 steps of size dt with heat_scale sigma
  *   fus_thermal_steps_sts   nsteps RKL2 steps of `stages` stages each; states and argument checks as fus_thermal_steps,
  *                        and FUS_ERR_ARG for stages outside 2..32
@@ -480,7 +482,32 @@ int fus_model_set_source(fus_model* model, const void* amplitude, const void* de
  *   One fus_op serves EITHER thermal steps OR wave steps at a time: both use its send / receive buffers and d_partial
  *   (for d_partial this was the rule already); calls in turns on the context's stream are fine, concurrent ones are not.
  *   Not covered: the external transport, graph capture of thermal steps, overlapping the exchange with part of the block
- *   kernel ("overlap_blocks" has no effect here). */
+ *   kernel ("overlap_blocks" has no effect here).
+ * Per-harmonic heat load (fus_thermal_set_heat_from_harmonics).  Tissue absorption grows with frequency, so the energy a
+ * nonlinear beam has moved into its harmonics heats faster than alpha at the source frequency times p_rms^2 says.  Let n be
+ * the monitor's sample count, C_k and S_k its cosine and sine accumulators (COS_k = 2 C_k / n, SIN_k = 2 S_k / n), K = nharm
+ * the number of harmonics asked for and alpha_k[e] >= 0 the amplitude absorption in Np/m of cell e at k times the source
+ * frequency:
+ *   a_k = (2 / n^2) (C_k^2 + S_k^2) = (COS_k^2 + SIN_k^2) / 2      the mean square of harmonic k
+ *   m_k = M(2 alpha_k / (rho c)) 1                                 the model's own c0, rho0 per cell, as the rms path uses them
+ *   h   = sum_{k = 1..K} m_k .* a_k                                W per DOF
+ * The sum over k is carried in double for both scalar types, in ascending k, as sum_k (double) m_k (C_k^2 + S_k^2), then
+ * scaled by 2 / n^2 and rounded to T once: the fp32 error does not grow with K.  The mean (DC) term and everything above
+ * harmonic K carry NO heat; with all alpha_k equal, h is the rms path's load of the signal minus its mean and minus
+ * that residual.  a_k is the mean square of harmonic k only over a window of whole source periods sampled uniformly with
+ * more than 2 K samples per period (fenicsxfus_amd.monitor.whole_period_window); the library does not check the window.
+ *   absorption   host T[nharm][ncells], caller cell numbering, row k - 1 = alpha_k
+ *   nharm        1..8 (else FUS_ERR_ARG), at most the monitor's own nharm (else FUS_ERR_STATE); fewer uses harmonics 1..nharm
+ * FUS_ERR_ARG: a null argument, a model on another fus_op, nharm outside 1..8, a negative or non-finite entry in any row.
+ * FUS_ERR_STATE: the monitor is off, watches FUS_V, has no sample, or holds fewer harmonics.  All are found before
+ * anything is enqueued; the heat load stays as it was and the monitor's accumulators are never altered.
+ * Device work, at setup time: per harmonic the lumped weight (the operator's two launches) and one streaming launch over
+ * one double scratch plane; fus_thermal_set_heat and fus_thermal_set_heat_from_monitor enqueue what they always did.
+ * Several ranks: a_k has the same bits on every sharer of a DOF because the states do, so the sharers' parts of h itself,
+ * sum_k m_k(part) .* a_k rounded to T, are summed in one ordered exchange (not K weights), and all sharers end with the
+ * same bits.  Under RCCL the call is collective and exchanges at once; in an in-process group the part waits for
+ * fus_group_thermal_finish like any heat load (on every member or none, and of the same kind on all of them);
+ * fus_thermal_set_heat(q = NULL) drops it. */
 typedef struct fus_thermal fus_thermal;
 enum { FUS_TH_RISE = 0, FUS_TH_DOSE = 1, FUS_TH_HEAT = 2 };
 int fus_thermal_create(fus_ctx* ctx, fus_op* op, const void* conductivity, const void* rho_c,
@@ -491,6 +518,8 @@ int fus_thermal_set(fus_thermal* thermal, int which, const void* in, int space);
 int fus_thermal_get(fus_thermal* thermal, int which, void* out, int space);
 int fus_thermal_set_heat(fus_thermal* thermal, const void* q, const void* q_coef, int space);
 int fus_thermal_set_heat_from_monitor(fus_thermal* thermal, fus_model* model, const void* absorption /* T[ncells], Np/m */);
+int fus_thermal_set_heat_from_harmonics(fus_thermal* thermal, fus_model* model, int nharm,
+                                        const void* absorption /* T[nharm][ncells], Np/m, row k - 1 = harmonic k */);
 int fus_thermal_lambda_max(fus_thermal* thermal, int iters, double* lambda);
 int fus_thermal_steps(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale);
 int fus_thermal_steps_sts(fus_thermal* thermal, double dt, int64_t nsteps, double heat_scale, int stages);

@@ -395,6 +395,13 @@ public:
   {
     check(fus_thermal_set_heat_from_monitor(h_, model.handle(), absorption));
   }
+  // per-harmonic heating sum_k 2 alpha_k |p_k|^2 / (2 rho c) from the monitor's harmonics 1..nharm (at most the monitor's
+  // own): absorption [nharm][ncells], row k - 1 = alpha at k times the source frequency (fusmi.h, per-harmonic heat load)
+  template <typename Model>
+  void set_heat_from(const Model& model, const T* absorption, int nharm)
+  {
+    check(fus_thermal_set_heat_from_harmonics(h_, model.handle(), nharm, absorption));
+  }
   // of m_C^-1 (K(k) + diag(m_W + m_H)) with the fixed DOFs removed (the boundary in force)
   double lambda_max(int iters = 20) const
   {
