@@ -3764,6 +3764,7 @@ int fus_group_finish_setup(fus_model** ms, int n)
 }
 
 static int model_after_step(fus_model* m, double t);   // field monitor, defined with fus_model_monitor below
+static int model_record_step(fus_model* m, double t);  // receiver recording, defined with fus_model_record below
 
 int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nsteps)
 {
@@ -3791,7 +3792,10 @@ int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nst
         std::swap(ms[i]->u_, ms[i]->u0), std::swap(ms[i]->v_, ms[i]->v0);
     t += dt;
     for (int i = 0; i < n; ++i)
+    {
+      FUSCHK(model_record_step(ms[i], t));
       FUSCHK(model_after_step(ms[i], t));
+    }
   }
   for (int i = 0; i < n; ++i)
     HIPCHK(hipStreamSynchronize(ms[i]->ctx->stream));
@@ -3886,7 +3890,10 @@ int fus_model_stage_end(fus_model* m, int stage, double t, double dt)
   if (stage == m->rk_order - 1 && m->rk_order != 4)
     std::swap(m->u_, m->u0), std::swap(m->v_, m->v0);  // the accumulated solution is the new state
   if (stage == m->rk_order - 1)
+  {
+    FUSCHK(model_record_step(m, t + dt));
     FUSCHK(model_after_step(m, t + dt));
+  }
   return FUS_OK;
 }
 
@@ -3968,8 +3975,11 @@ static int model_record_step(fus_model* m, double t)
   ++m->rec_step;
   if (m->rec_step % m->rec_every != 0 || m->rec_n >= m->rec_cap)
     return FUS_OK;
-  launch_sample(m, m->rec_which, static_cast<char*>(m->d_rec) + (size_t)m->rec_n * m->rc_n * m->op->ts);
-  HIPCHK(hipGetLastError());
+  if (m->rc_n > 0)  // a rank that holds none of the receivers still counts the record and its time
+  {
+    launch_sample(m, m->rec_which, static_cast<char*>(m->d_rec) + (size_t)m->rec_n * m->rc_n * m->op->ts);
+    HIPCHK(hipGetLastError());
+  }
   m->rec_times.push_back(t);
   ++m->rec_n;
   return FUS_OK;

@@ -151,7 +151,9 @@ class _SpectralExplicit:
         return out
 
     def record(self, every: int, capacity: int, which: str = "u"):
-        """Sample the receivers after every ``every``-th step of rk() / rk4_steps() into a device buffer."""
+        """Sample the receivers after every ``every``-th step into a device buffer of ``capacity`` records: the steps of
+        rk() / rk4_steps(), of group_rk4_steps() (every slab model records its own receivers) and of the external stage
+        loop (stage_end of a step's last stage).  A rank that holds no receiver still counts the records and times."""
         w = _abi.FUS_U if which == "u" else _abi.FUS_V
         check(lib().fus_model_record(self.h, C.c_int(w), C.c_int(every), C.c_int64(capacity)))
 

@@ -267,8 +267,11 @@ int64_t fus_model_ndofs(fus_model* model); /* number_of_dofs(), Linear.hpp:318 (
  * keeps, per receiver, the internal indices of its cell's dofs and the 1-D Lagrange basis values, and evaluates
  * u_h (FUS_U) or v_h (FUS_V) at the receivers from the vectors resident in HBM -- no full-vector copy.
  *   fus_model_sample       T[npts] now, into host or device memory (`space`)
- *   fus_model_record       sample `which` after every `every`-th step of fus_model_rk4 / fus_model_rk4_steps into a
- *                          device buffer of `capacity` records (every = 0: off); restarts the record count
+ *   fus_model_record       sample `which` after every `every`-th step into a device buffer of `capacity` records
+ *                          (every = 0: off); restarts the record count.  A step is one of fus_model_rk4 /
+ *                          fus_model_rk4_steps, of fus_group_rk4_steps (every member records by itself) or, under the
+ *                          external transport, the fus_model_stage_end of a step's last stage (time t + dt).  A rank
+ *                          that holds none of the receivers (npts = 0) counts its records and their times all the same
  *   fus_model_get_records  copies the records taken so far (T[nrec*npts], row = record) and their times; out / times
  *                          may be NULL to query *nrec only */
 int fus_model_set_receivers(fus_model* model, int64_t npts, const int32_t* cells, const double* refcoords);

@@ -247,7 +247,8 @@ public:
     check(fus_model_sample(h_, which, out.data(), FUS_HOST));
     return out;
   }
-  // sample after every `every`-th step of rk4 / rk4_steps into a device buffer of `capacity` records
+  // sample after every `every`-th step of rk4 / rk4_steps -- or of fus_group_rk4_steps, or at the last fus_model_stage_end of
+  // a step under the external transport -- into a device buffer of `capacity` records
   void record(int every, std::int64_t capacity, int which = FUS_U) { check(fus_model_record(h_, which, every, capacity)); }
   std::vector<T> records(std::vector<double>* times = nullptr) const
   {

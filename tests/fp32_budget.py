@@ -59,8 +59,8 @@ def errors(a, r64, regions):
     return out
 
 
-def yardstick(r32, r64, regions):
-    return {k: max(e, EPS32) for k, e in errors(r32, r64, regions).items()}
+def yardstick(r32, r64, regions, floor=EPS32):
+    return {k: max(e, floor) for k, e in errors(r32, r64, regions).items()}
 
 
 def as_fields(x):
@@ -71,12 +71,13 @@ def as_fields(x):
     return {"y": x}
 
 
-def budget(g, r32, r64, regions):
-    """(largest ratio err(g, R) / yard(R), (field, measure) where it occurred, {field: {measure: (err, yard)}})."""
+def budget(g, r32, r64, regions, floor=EPS32):
+    """(largest ratio err(g, R) / yard(R), (field, measure) where it occurred, {field: {measure: (err, yard)}}).
+    ``floor``: one ulp of the type under test (the receivers' fp64 cases pass 2^-52, receiver_ref.py)."""
     g, r32, r64 = as_fields(g), as_fields(r32), as_fields(r64)
     worst, where, table = -1.0, None, {}
     for f in r64:
-        e, y = errors(g[f], r64[f], regions), yardstick(r32[f], r64[f], regions)
+        e, y = errors(g[f], r64[f], regions), yardstick(r32[f], r64[f], regions, floor)
         table[f] = {k: (e[k], y[k]) for k in e}
         for k in e:
             if e[k] / y[k] > worst:
