@@ -19,10 +19,13 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
+#include <utility>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "block_variant.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
 #include "sts_coef.hpp"
@@ -222,12 +225,12 @@ struct fus_op
   size_t lds_bytes = 0;
   int deterministic = 0;
   int nfields = 1;
-  bool affine = false;     // GEOM_AFFINE path in use (d_Gc), streamed G/detJ built only on demand
-  bool trilinear = false;  // GEOM_TRILINEAR path in use (d_Gc holds 21 map coefficients per cell)
-  bool mfma = false;       // MFMA contraction variants of the block kernel in use (degrees 6, 7)
-  bool ortho_mesh = false; // every cell a parallelepiped with mutually orthogonal edges (found in op_build)
-  bool diag = false;       // GEOM_AFFINE in its diagonal-metric form (ortho_mesh, degrees <= 7, option "diag_metric")
-  bool pk = false;         // packed fp32 variants in use (degrees 5-7: two elements per wave, layout slots doubled)
+  // what decides the block kernel's variant (block_variant.hpp).  op_build fills both with the geometry mode it predicts
+  // (facts.mode; facts.ortho is found there); op_setup_device puts in the mode the device confirmed -- GEOM_AFFINE: per-cell
+  // factors in d_Gc, streamed G / detJ built only on demand; GEOM_TRILINEAR: d_Gc holds 21 map coefficients per cell --
+  // and settles traits.mfma and traits.diag; traits.pk stays what the layout was built with
+  OpFacts facts{};
+  OpTraits traits{};
   void* d_Gc = nullptr;
   void *d_xg = nullptr, *d_pts = nullptr, *d_wts = nullptr;
   int32_t* d_xdm = nullptr;
@@ -339,6 +342,25 @@ static int upload(std::vector<void*>& pool, U** p, const std::vector<U>& v, hipS
   return FUS_OK;
 }
 static inline unsigned nblk(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+
+// A run-time integer as a template argument: f(std::integral_constant<int, K>{}) for the K of the list that equals
+// `kind`; f returns a status.  A kind outside the list is an error, never some other kernel.
+template <int... Ks, typename F>
+static int with_kind(int kind, F&& f)
+{
+  int r = FUS_OK;
+  if (((kind == Ks && ((r = f(std::integral_constant<int, Ks>{})), true)) || ...))
+    return r;
+  return fail(FUS_ERR_STATE, "no kernel variant of kind " + std::to_string(kind));
+}
+template <typename F, int... Ks>
+static int with_kind(int kind, F&& f, std::integer_sequence<int, Ks...>)
+{
+  return with_kind<Ks...>(kind, f);
+}
+
+// fn<double>(...) or fn<float>(...) by a FUS_F64 / FUS_F32 scalar type
+#define FUS_BY_DTYPE(dtype, fn, ...) ((dtype) == FUS_F64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
 struct ProfScope
 {
@@ -463,86 +485,20 @@ static int launch_block_op(fus_op* op, const T* geo, const T* coef, const T* x, 
     return fail(FUS_ERR_STATE, "operator data was not created for two-field models (option fields=2)");
   if (blk_count < 0)
     blk_count = op->L.nblocks - blk_begin;
-  const int b0 = blk_begin, nb = blk_count;
-  if constexpr (P >= 8)
+  // which kernel (block_variant.hpp), then the five integers as template arguments: of the keys only those whose
+  // kernel exists for <T, P, OP, STAGE> are compiled in
+  const BlockVariant v = block_variant(op->facts, op->traits, OP, STAGE);
+  const T* g = v.geom == GEOM_STREAM ? geo : static_cast<const T*>(op->d_Gc);   // streamed per-point arrays or per-cell factors
+  constexpr int NO_KERNEL = std::numeric_limits<int>::min();
+  const int r = with_kind(block_variant_key(v), [&](auto K) -> int
   {
-    // degrees 8-10: two waves per element (kernels.hpp, elem_compute_hi); per-cell geometry where the mesh allows,
-    // per-point factors streamed otherwise (second-order geometry, option "geometry" = 1)
-    if (op->tdim == 2)   // quadrilaterals: an element's N^2 nodes span two waves (elem_compute2d, HI)
-      return op->deterministic
-                 ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_STREAM, 2>(op, geo, coef, x, bvec, S, b0, nb)
-                 : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_STREAM, 2>(op, geo, coef, x, bvec, S, b0, nb);
-    if (!(op->affine || op->trilinear))
-      return op->deterministic
-                 ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_STREAM>(op, geo, coef, x, bvec, S, b0, nb)
-                 : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_STREAM>(op, geo, coef, x, bvec, S, b0, nb);
-    const T* gc = static_cast<const T*>(op->d_Gc);
-    if (op->affine)
-      return op->deterministic
-                 ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_AFFINE>(op, gc, coef, x, bvec, S, b0, nb)
-                 : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_AFFINE>(op, gc, coef, x, bvec, S, b0, nb);
-    return op->deterministic
-               ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_TRILINEAR>(op, gc, coef, x, bvec, S, b0, nb)
-               : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_TRILINEAR>(op, gc, coef, x, bvec, S, b0, nb);
-  }
-  else
-  {
-  if (op->tdim == 2)  // quadrilaterals: streamed geometry only
-    return op->deterministic
-               ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_STREAM, 2>(op, geo, coef, x, bvec, S, b0, nb)
-               : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_STREAM, 2>(op, geo, coef, x, bvec, S, b0, nb);
-  // degrees 6 and 7, per-cell geometry, LDS-atomic accumulation: the index-1 / index-2 contractions on the
-  // matrix cores (kernels.hpp, elem_compute_mfma) where option "mfma" / the measured default says so; the
-  // variants exist for the stiffness operator as the plain action and as the lean RK4 stages
-  if constexpr ((P == 6 || P == 7) && OP == OP_STIFFNESS && (STAGE == STAGE_NONE || STAGE >= 3))
-  {
-    if (op->mfma && !op->deterministic && op->tdim == 3 && (op->affine || op->trilinear))
-    {
-      const T* gc = static_cast<const T*>(op->d_Gc);
-      return op->affine ? launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_AFFINE, 3, 1>(op, gc, coef, x, bvec, S, b0, nb)
-                        : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_TRILINEAR, 3, 1>(op, gc, coef, x, bvec, S, b0, nb);
-    }
-  }
-  // fp32, degrees 5-7, per-cell geometry, LDS-atomic accumulation: two elements per wave in packed float2
-  // (kernels.hpp, elem_compute_pk); stiffness operator only (the mass action runs through the scalar kernel)
-  if constexpr (sizeof(T) == 4 && P >= 5 && P <= 7 && OP == OP_STIFFNESS)
-  {
-    if (op->pk && !op->mfma && !op->deterministic && op->tdim == 3 && (op->affine || op->trilinear))
-    {
-      const T* gc = static_cast<const T*>(op->d_Gc);
-      return op->affine ? launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_AFFINE, 3, 0, 1>(op, gc, coef, x, bvec, S, b0, nb)
-                        : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_TRILINEAR, 3, 0, 1>(op, gc, coef, x, bvec, S, b0, nb);
-    }
-  }
-  // geometry operand: per-cell factors (affine meshes) or the streamed per-point arrays
-  if constexpr (OP == OP_STIFFNESS && P <= 7)
-  {
-    if (op->affine && op->diag)   // cells with orthogonal edges: diagonal-metric form of the stiffness action
-    {
-      const T* gc = static_cast<const T*>(op->d_Gc);
-      return op->deterministic
-                 ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_DIAG>(op, gc, coef, x, bvec, S, b0, nb)
-                 : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_DIAG>(op, gc, coef, x, bvec, S, b0, nb);
-    }
-  }
-  if (op->affine)
-  {
-    const T* gc = static_cast<const T*>(op->d_Gc);
-    return op->deterministic
-               ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_AFFINE>(op, gc, coef, x, bvec, S, b0, nb)
-               : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_AFFINE>(op, gc, coef, x, bvec, S, b0, nb);
-  }
-  if (op->trilinear)
-  {
-    const T* gc = static_cast<const T*>(op->d_Gc);
-    return op->deterministic
-               ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_TRILINEAR>(op, gc, coef, x, bvec, S, b0, nb)
-               : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_TRILINEAR>(op, gc, coef, x, bvec, S, b0, nb);
-  }
-  return op->deterministic
-             ? launch_block_op_v<T, P, OP, 0, STAGE, NF, GEOM_STREAM>(op, geo, coef, x, bvec, S, b0, nb)
-             : launch_block_op_v<T, P, OP, 1, STAGE, NF, GEOM_STREAM>(op, geo, coef, x, bvec, S, b0, nb);
-  }
+    constexpr BlockVariant V = block_variant_of_key(decltype(K)::value);
+    if constexpr (block_variant_exists(P, sizeof(T), OP, STAGE, V))
+      return launch_block_op_v<T, P, OP, V.atomic, STAGE, NF, V.geom, V.td, V.mf, V.pk>(op, g, coef, x, bvec, S, blk_begin, blk_count);
+    else
+      return NO_KERNEL;
+  }, std::make_integer_sequence<int, block_variant_nkeys>{});
+  return r != NO_KERNEL ? r : fail(FUS_ERR_STATE, "this library holds no block kernel for the variant asked for");
 }
 
 template <typename T>
@@ -579,8 +535,9 @@ static int apply_internal(fus_op* op, const T* coef, const T* x, T* bvec)
 // between them: pack (own partials -> send buffers), exchange (RCCL send/recv over xGMI, or
 // device copies for the in-process transport), unpack (ordered sum).
 template <typename T>
-static int halo_pack(fus_op* op, const T* vec)
+static int halo_pack(fus_op* op, const void* vec_)
 {
+  const T* vec = static_cast<const T*>(vec_);
   if (op->neigh.empty())
     return FUS_OK;
   fus_ctx* c = op->ctx;
@@ -616,8 +573,9 @@ static int halo_exchange_rccl(fus_op* op)
 }
 
 template <typename T>
-static int halo_unpack(fus_op* op, T* vec)
+static int halo_unpack(fus_op* op, void* vec_)
 {
+  T* vec = static_cast<T*>(vec_);
   fus_ctx* c = op->ctx;
   if (op->neigh.empty())
     return FUS_OK;
@@ -632,7 +590,7 @@ static int halo_unpack(fus_op* op, T* vec)
 
 // RCCL transport: the three phases back to back
 template <typename T>
-static int halo_sum(fus_op* op, T* vec)
+static int halo_sum(fus_op* op, void* vec)
 {
   if (op->neigh.empty())
     return FUS_OK;
@@ -711,17 +669,12 @@ static int ensure_stream_geometry(fus_op* op)
   return FUS_OK;
 }
 
-// Measured choice (MI355X, profiles/r02_experiments.md sections 5 and 15) between the vector and the matrix-core
-// form of the index-1 / index-2 contractions.
-static bool mfma_default(int P, bool f64, bool affine)
+// The facts behind the block kernel's variant (block_variant.hpp) for geometry mode `mode`, with the options as the
+// context holds them now
+static OpFacts op_facts(const fus_op* op, int mode, bool ortho, int deterministic)
 {
-  // Nowhere at present.  Degree 7, fp64, trilinear geometry was the one case where the matrix-core form won
-  // (-5.8 % against the tile-read vector form); with the re-mapped vector contractions at N = 8 (derivative-table
-  // rows by scalar loads) the vector form is 2.7 % ahead: 1.423 against 1.469 ms per launch at 64^3.  Affine
-  // geometry at degree 7 (+6 %: little vector work to relieve) and fp32 at degree 6 (+45 %: the f32 MFMA issues
-  // at the vector-FMA rate) were slower from the start.  Option "mfma" = 1 still selects the variants.
-  (void)P, (void)f64, (void)affine;
-  return false;
+  const fus_ctx* c = op->ctx;
+  return {op->P, (int)op->ts, op->tdim, op->geom_order, mode, ortho, deterministic != 0, c->mfma, c->pack32, c->diag_metric};
 }
 
 template <typename T, int P>
@@ -818,22 +771,19 @@ static int op_setup_device(fus_op* op)
     memcpy(&rel_err, &err_bits, sizeof(float));
   }
   op->d_Gc = d_Gc;
-  op->affine = c->geometry == 0 && rel_err <= (sizeof(T) == 8 ? 1e-12f : 1e-6f);
-  op->trilinear = !op->affine && c->geometry != 1 && op->geom_order == 1 && op->tdim == 3;
-  // matrix-core contraction variants: degrees 6 and 7 on the per-cell geometry paths; "auto" follows the
-  // A/B measurements on MI355X (profiles/r02_mfma.md)
-  op->mfma = (P == 6 || P == 7) && (op->affine || op->trilinear) && !op->deterministic
-             && (c->mfma == 1 || (c->mfma < 0 && mfma_default(P, sizeof(T) == 8, op->affine)));
-  op->diag = op->affine && op->ortho_mesh && c->diag_metric && P <= 7 && !op->mfma && !op->pk;
-  if (op->affine)
-    op->lds_bytes = L.lds_bytes(sizeof(T), op->nfields, 7);
-  else if (op->trilinear)
+  const bool affine = c->geometry == 0 && rel_err <= (sizeof(T) == 8 ? 1e-12f : 1e-6f);
+  const bool trilinear = !affine && c->geometry != 1 && op->geom_order == 1 && op->tdim == 3;
+  // the confirmed mode settles the traits; the layout's pk is a fact by now
+  op->facts = op_facts(op, affine ? GEOM_AFFINE : (trilinear ? GEOM_TRILINEAR : GEOM_STREAM), op->facts.ortho, op->deterministic);
+  op->traits = op_traits(op->facts, op->traits.pk);
+  if (trilinear)
   {
     hipLaunchKernelGGL((k_geometry_trilinear<T>), dim3(nblk(op->ncells)), dim3(256), 0, st, op->ncells,
                        op->d_cell_perm, d_xg, op->d_xdm, d_Gc);
     HIPCHK(hipGetLastError());
-    op->lds_bytes = L.lds_bytes(sizeof(T), op->nfields, 21);
   }
+  if (op->traits.gcs)
+    op->lds_bytes = L.lds_bytes(sizeof(T), op->nfields, op->traits.gcs);
   else
     FUSCHK((ensure_stream_geometry<T, P>(op)));
 
@@ -1279,17 +1229,18 @@ static StageScalars stage_scalars(const fus_model* m, int i, double t_, double d
   return sc;
 }
 
-// Which fused-update variant stage i uses: 0 = first stage (reads u0, v0 only), 1 = middle stage,
-// 3 = last stage of RK4 (writes the new u0, v0 directly).  The lower-order schemes end on a middle
-// stage and swap (u_, v_) with (u0, v0) afterwards.
+// Which fused-update variant stage i uses: STAGE_FIRST (reads u0, v0 only), STAGE_MID, STAGE_LAST = last stage of RK4
+// (writes the new u0, v0 directly).  The lower-order schemes end on a middle stage and swap (u_, v_) with (u0, v0) afterwards.
 static int stage_kind(const fus_model* m, int i)
 {
   if (m->rk_order == 4 && m->lean_rk4)   // classical RK4 without accumulator streams (kernels.hpp, stage kinds 4-7)
-    return 4 + i;
+    return STAGE_LEAN0 + i;
   if (i == 0)
-    return 0;
-  return (m->rk_order == 4 && i == 3) ? 3 : 1;
+    return STAGE_FIRST;
+  return (m->rk_order == 4 && i == 3) ? STAGE_LAST : STAGE_MID;
 }
+// every kind stage_kind returns: the instantiations of the stage kernels
+#define FUS_STAGE_KINDS STAGE_FIRST, STAGE_MID, STAGE_LAST, STAGE_LEAN0, STAGE_LEAN1, STAGE_LEAN2, STAGE_LEAN3
 
 // The stage's velocity buffers as the fused updates name them.  Stage kinds 0, 1, 3: the model's own vn, v_, u_.
 // Lean RK4 (kinds 4-7): the three stage velocities V_1, V_2, V_3 rotate through those three buffers (A = vn, B = v_,
@@ -1373,27 +1324,15 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   const T* G = static_cast<const T*>(op->d_G);
   const T* coef = static_cast<const T*>(m->coef);
   const int kind = stage_kind(m, i);
+  const bool two_fields = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
   auto launch = [&](int b0, int nb) -> int
   {
-#define FUS_STAGE_CASE(K, NFV)                                                                       \
-  case K:                                                                                          \
-    return launch_block_op<T, P, OP_STIFFNESS, K, NFV>(op, G, coef, ustage, b, S, b0, nb);
-    if (m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT)
+    return with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      switch (kind)
-      {
-        FUS_STAGE_CASE(0, 2) FUS_STAGE_CASE(3, 2) FUS_STAGE_CASE(4, 2) FUS_STAGE_CASE(5, 2) FUS_STAGE_CASE(6, 2) FUS_STAGE_CASE(7, 2)
-      default:
-        return launch_block_op<T, P, OP_STIFFNESS, 1, 2>(op, G, coef, ustage, b, S, b0, nb);
-      }
-    }
-    switch (kind)
-    {
-      FUS_STAGE_CASE(0, 1) FUS_STAGE_CASE(3, 1) FUS_STAGE_CASE(4, 1) FUS_STAGE_CASE(5, 1) FUS_STAGE_CASE(6, 1) FUS_STAGE_CASE(7, 1)
-    default:
-      return launch_block_op<T, P, OP_STIFFNESS, 1>(op, G, coef, ustage, b, S, b0, nb);
-    }
-#undef FUS_STAGE_CASE
+      constexpr int KIND = decltype(K)::value;
+      return two_fields ? launch_block_op<T, P, OP_STIFFNESS, KIND, 2>(op, G, coef, ustage, b, S, b0, nb)
+                        : launch_block_op<T, P, OP_STIFFNESS, KIND, 1>(op, G, coef, ustage, b, S, b0, nb);
+    });
   };
   // Multi-rank, option "overlap_blocks": the blocks that touch interface dofs (first in the layout)
   // run ahead, their partials are reduced, packed and handed to the exchange, and the remaining
@@ -1509,41 +1448,25 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     PL.bnd0 = (int32_t)op->L.n_partial;
     for (size_t j = 0; j < op->L.plane_cnt.size(); ++j)
       PL.cnt[j] = (int32_t)op->L.plane_cnt[j], PL.off[j] = (int32_t)op->L.plane_off[j];
-#define FUS_PLANES_CASE(K)                                                                         \
-  case K:                                                                                          \
-    hipLaunchKernelGGL((k_shared_stage_planes<T, K>), grid, blk, 0, st, nloc, PL, m->d_bnd_mask, m->d_bnd_base,      \
-                       partial, minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt,    \
-                       m0p, mn1p, B, R);                                                           \
-    break;
-    switch (kind)
+    FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      FUS_PLANES_CASE(0) FUS_PLANES_CASE(3) FUS_PLANES_CASE(4) FUS_PLANES_CASE(5) FUS_PLANES_CASE(6) FUS_PLANES_CASE(7)
-    default:
-      hipLaunchKernelGGL((k_shared_stage_planes<T, 1>), grid, blk, 0, st, nloc, PL, m->d_bnd_mask, m->d_bnd_base,
+      hipLaunchKernelGGL((k_shared_stage_planes<T, decltype(K)::value>), grid, blk, 0, st, nloc, PL, m->d_bnd_mask, m->d_bnd_base,
                          partial, minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt,
                          m0p, mn1p, B, R);
-    }
-#undef FUS_PLANES_CASE
+      return FUS_OK;
+    }));
   }
   else if (nloc > 0)
   {
     ProfScope ps(c, "stage");
     const dim3 grid(nblk(nloc)), blk(256);
-#define FUS_SHARED_CASE(K)                                                                         \
-  case K:                                                                                          \
-    hipLaunchKernelGGL((k_shared_stage<T, K>), grid, blk, 0, st, nloc, m->d_sh_ptr32, m->d_sh_pairs32, partial,      \
-                       minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt, m0p, mn1p, B, \
-                       R);                                                                         \
-    break;
-    switch (kind)
+    FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      FUS_SHARED_CASE(0) FUS_SHARED_CASE(3) FUS_SHARED_CASE(4) FUS_SHARED_CASE(5) FUS_SHARED_CASE(6) FUS_SHARED_CASE(7)
-    default:
-      hipLaunchKernelGGL((k_shared_stage<T, 1>), grid, blk, 0, st, nloc, m->d_sh_ptr32, m->d_sh_pairs32, partial,
+      hipLaunchKernelGGL((k_shared_stage<T, decltype(K)::value>), grid, blk, 0, st, nloc, m->d_sh_ptr32, m->d_sh_pairs32, partial,
                          minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt, m0p, mn1p, B,
                          R);
-    }
-#undef FUS_SHARED_CASE
+      return FUS_OK;
+    }));
   }
   if (!op->neigh.empty())
   {
@@ -1556,21 +1479,13 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     const T* recv = static_cast<const T*>(op->d_recvbuf);
     const T* m0f = m->mn1 ? static_cast<const T*>(m->m) : nullptr;
     const T* mn1f = m->mn1 ? static_cast<const T*>(m->mn1) : nullptr;
-#define FUS_IF_CASE(K)                                                                             \
-  case K:                                                                                          \
-    hipLaunchKernelGGL((k_if_unpack_stage<T, K>), grid, blk, 0, st, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc,  \
-                       recv, b, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0f, mn1f, op->L.n_int_pad, m->d_sh_ptr32,    \
-                       m->d_sh_pairs32, B, R);                                                     \
-    break;
-    switch (kind)
+    FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      FUS_IF_CASE(0) FUS_IF_CASE(3) FUS_IF_CASE(4) FUS_IF_CASE(5) FUS_IF_CASE(6) FUS_IF_CASE(7)
-    default:
-      hipLaunchKernelGGL((k_if_unpack_stage<T, 1>), grid, blk, 0, st, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc,
+      hipLaunchKernelGGL((k_if_unpack_stage<T, decltype(K)::value>), grid, blk, 0, st, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc,
                          recv, b, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0f, mn1f, op->L.n_int_pad, m->d_sh_ptr32,
                          m->d_sh_pairs32, B, R);
-    }
-#undef FUS_IF_CASE
+      return FUS_OK;
+    }));
   }
   HIPCHK(hipGetLastError());
   return FUS_OK;
@@ -1802,29 +1717,11 @@ static int d_stage_begin(fus_model* m, int i, double t, double dt)
   FUS_DEGREE(d, m->op->dtype, m->op->P);
   return d->stage_begin(m, i, t, dt);
 }
-static int d_stage_end(fus_model* m, int i, double t, double dt)
-{
-  return m->op->dtype == FUS_F64 ? stage_end<double>(m, i, t, dt) : stage_end<float>(m, i, t, dt);
-}
-static int d_setup_finish(fus_model* m)
-{
-  return m->op->dtype == FUS_F64 ? model_setup_finish<double>(m) : model_setup_finish<float>(m);
-}
-static int d_halo_sum(fus_op* op, void* v)
-{
-  return op->dtype == FUS_F64 ? halo_sum<double>(op, static_cast<double*>(v))
-                              : halo_sum<float>(op, static_cast<float*>(v));
-}
-static int d_halo_pack(fus_op* op, const void* v)
-{
-  return op->dtype == FUS_F64 ? halo_pack<double>(op, static_cast<const double*>(v))
-                              : halo_pack<float>(op, static_cast<const float*>(v));
-}
-static int d_halo_unpack(fus_op* op, void* v)
-{
-  return op->dtype == FUS_F64 ? halo_unpack<double>(op, static_cast<double*>(v))
-                              : halo_unpack<float>(op, static_cast<float*>(v));
-}
+static int d_stage_end(fus_model* m, int i, double t, double dt) { return FUS_BY_DTYPE(m->op->dtype, stage_end, m, i, t, dt); }
+static int d_setup_finish(fus_model* m) { return FUS_BY_DTYPE(m->op->dtype, model_setup_finish, m); }
+static int d_halo_sum(fus_op* op, void* v) { return FUS_BY_DTYPE(op->dtype, halo_sum, op, v); }
+static int d_halo_pack(fus_op* op, const void* v) { return FUS_BY_DTYPE(op->dtype, halo_pack, op, v); }
+static int d_halo_unpack(fus_op* op, void* v) { return FUS_BY_DTYPE(op->dtype, halo_unpack, op, v); }
 
 // (Re)build the block layout and the device-side operator data.  force_shared marks dofs held by
 // other ranks too: they must never be finished inside a block's fused epilogue.
@@ -1886,9 +1783,14 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
           ortho_mesh = false;
       }
   }
-  op->ortho_mesh = affine_mesh && ortho_mesh;
-  // diagonal-metric form of the affine kernel: scalar kernels of the degrees <= 7 (no packed / matrix-core variant)
-  const bool diag_mesh = op->ortho_mesh && c->diag_metric && op->P <= 7 && !(c->mfma == 1) && !(c->pack32 == 1);
+  // first-order hexahedra that are not all affine: J and G recomputed per point from each cell's
+  // trilinear map (GEOM_TRILINEAR) unless the streamed factors are asked for; else: per-point factors streamed
+  const bool trilinear_mesh = !affine_mesh && c->geometry != 1 && op->geom_order == 1 && op->tdim == 3;
+  // the traits of the predicted mode: whether the layout gets the packed kernel's two slots, and the LDS budget
+  op->facts = op_facts(op, affine_mesh ? GEOM_AFFINE : (trilinear_mesh ? GEOM_TRILINEAR : GEOM_STREAM),
+                       affine_mesh && ortho_mesh, c->deterministic);
+  op->traits = op_traits(op->facts);
+  const int gcs = op->traits.gcs;
   // auto block size: about 2-3 thousand local dofs per block when G is streamed (128 / 64 / 32
   // elements at P = 2 / 3 / >= 4; larger P shrink further to fit LDS), half of that on the affine
   // path (profiles/r01_block_sweep.txt)
@@ -1896,17 +1798,14 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
   if (op->P >= 8)
   {
     // degrees 8-10 (two waves per element): 4-element blocks, an even number of waves
-    const bool aff = affine_mesh;
-    const bool tri8 = !affine_mesh && c->geometry != 1 && op->geom_order == 1 && op->tdim == 3;   // else: per-point factors streamed
-    const int gcs8 = aff ? 7 : (tri8 ? 21 : 0);
     int waves8 = c->waves > 0 ? std::min(4, (c->waves + 1) & ~1) : 4;
     // (fp64 distorted cells at degree 8: 8-element blocks, +8.5 % over 4 -- fewer shared dofs; profiles/r03_experiments.md 7)
-    const int be_hi = op->tdim == 2 ? 32 : ((op->P == 8 && op->dtype == FUS_F64 && tri8) ? 8 : 4);
+    const int be_hi = op->tdim == 2 ? 32 : ((op->P == 8 && op->dtype == FUS_F64 && trilinear_mesh) ? 8 : 4);
     for (int be = c->block_elems > 0 ? c->block_elems : be_hi;; be = (be + 1) / 2)
     {
       std::string err = build_layout(op->L, op->P, op->ncells, op->ndofs, op->h_dofmap.data(), cen.data(), be, waves8,
                                      force_shared, op->tdim);
-      const bool too_big = err.empty() ? op->L.lds_bytes(op->ts, op->nfields, gcs8) + 64 > 160 * 1024
+      const bool too_big = err.empty() ? op->L.lds_bytes(op->ts, op->nfields, gcs) + 64 > 160 * 1024
                                        : err.find("65535") != std::string::npos;
       if (too_big && be > 1)
         continue;
@@ -1935,9 +1834,6 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
   // set there (kernels.hpp, FUS_PF1) and fits two waves per SIMD, which pays only if two blocks per
   // CU are resident: blocks of at most 80 KB of LDS (20 / 12 / 8 elements at p = 5 / 6 / 7 with one
   // operator input, fewer with two).  +50 / +30 / +35 % over one 32->16-element block per CU.
-  // first-order hexahedra that are not all affine: J and G recomputed per point from each cell's
-  // trilinear map (GEOM_TRILINEAR) unless the streamed factors are asked for
-  const bool trilinear_mesh = !affine_mesh && c->geometry != 1 && op->geom_order == 1 && op->tdim == 3;
   const bool two_per_cu = op->dtype == FUS_F64 && op->tdim == 3 && op->P >= 5 && !affine_mesh && !trilinear_mesh
                           && c->block_elems <= 0;
   static const int be_two[8] = {0, 0, 0, 0, 0, 20, 12, 8};
@@ -1949,13 +1845,6 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
   static const int be_aff_hi[8] = {0, 0, 0, 0, 0, 8, 8, 8};
   const int be_affine = (op->tdim == 3 && op->P >= 5) ? ((op->dtype == FUS_F32 && op->P == 7) ? 4 : be_aff_hi[op->P])
                                                       : be_stream / 2;
-  const int gcs = affine_mesh ? 7 : (trilinear_mesh ? 21 : 0);
-  // packed fp32 kernels (two elements per wave): degrees 5-7, per-cell geometry, LDS atomics, MFMA variants off
-  // "auto" = where it measured faster on MI355X (profiles/r02_experiments.md section 7): degree 5 (+4 %) and degree 6
-  // on affine cells (+2 %); slower at degree 6 trilinear (-12 %: 137 registers, three waves per SIMD) and degree 7
-  op->pk = op->dtype == FUS_F32 && op->tdim == 3 && op->P >= 5 && op->P <= 7 && (affine_mesh || trilinear_mesh)
-           && !c->deterministic && c->mfma != 1
-           && (c->pack32 == 1 || (c->pack32 < 0 && !diag_mesh && (op->P == 5 || (op->P == 6 && affine_mesh))));
   // fp32 halves the LDS per block: the trilinear kernel takes 16 elements at p >= 5 (+9-12 %), the
   // affine one at p = 5 only (+5 %; 16 is 2-9 % slower at p = 6, 7)
   // (round 3, fp64 accumulator: 16 / 8 / 8 elements at p = 5 / 6 / 7)
@@ -1983,7 +1872,7 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
   for (int be = be0;; be = two_per_cu && be > 4 ? be - std::max(1, be / 4) : (be + 1) / 2)
   {
     std::string err = build_layout(op->L, op->P, op->ncells, op->ndofs, op->h_dofmap.data(),
-                                   cen.data(), be, waves, force_shared, op->tdim, op->pk ? 2 : 1);
+                                   cen.data(), be, waves, force_shared, op->tdim, op->traits.pk ? 2 : 1);
     const bool too_big = err.empty() ? op->L.lds_bytes(op->ts, op->nfields, gcs) + 64 > lds_cap
                                      : err.find("65535") != std::string::npos;
     if (too_big && be > 1)
@@ -2336,14 +2225,14 @@ static int thermal_rk4_end(fus_thermal* th, int i, double dt_, double sigma)
   A.dose = th->dose;
   A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
   A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
+  const int kind = i == 0 ? STAGE_FIRST : (i < 3 ? STAGE_MID : STAGE_LAST);
   {
     ProfScope ps(c, "thermal");
-    if (i == 0)
-      hipLaunchKernelGGL((k_thermal_stage<T, 0>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
-    else if (i < 3)
-      hipLaunchKernelGGL((k_thermal_stage<T, 1>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
-    else
-      hipLaunchKernelGGL((k_thermal_stage<T, 3>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
+    FUSCHK((with_kind<STAGE_FIRST, STAGE_MID, STAGE_LAST>(kind, [&](auto K) -> int
+    {
+      hipLaunchKernelGGL((k_thermal_stage<T, decltype(K)::value>), dim3(grid), dim3(256), 0, c->stream, nvec, A);
+      return FUS_OK;
+    })));
     HIPCHK(hipGetLastError());
   }
   if (multi)
@@ -2353,12 +2242,11 @@ static int thermal_rk4_end(fus_thermal* th, int i, double dt_, double sigma)
     ProfScope ps(c, "thermal_if");
     const dim3 gi(nblk(op->n_uidx)), blk(256);
     const T* recv = static_cast<const T*>(op->d_recvbuf);
-    if (i == 0)
-      hipLaunchKernelGGL((k_thermal_if_stage<T, 0>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
-    else if (i < 3)
-      hipLaunchKernelGGL((k_thermal_if_stage<T, 1>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
-    else
-      hipLaunchKernelGGL((k_thermal_if_stage<T, 3>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    FUSCHK((with_kind<STAGE_FIRST, STAGE_MID, STAGE_LAST>(kind, [&](auto K) -> int
+    {
+      hipLaunchKernelGGL((k_thermal_if_stage<T, decltype(K)::value>), gi, blk, 0, c->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+      return FUS_OK;
+    })));
     HIPCHK(hipGetLastError());
   }
   return FUS_OK;
@@ -2413,14 +2301,14 @@ static int thermal_sts_end(fus_thermal* th, int j, double dt_, double sigma, con
   A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
   A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
   A.dt120 = dt_ / 120.0, A.t_base = th->t_base;
+  const int pos = j == 1 ? 0 : (j < c.s ? 1 : 2);   // first, middle, last stage of the step (k_thermal_sts_stage)
   {
     ProfScope ps(cx, "thermal_sts");
-    if (j == 1)
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 0>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
-    else if (j < c.s)
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 1>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
-    else
-      hipLaunchKernelGGL((k_thermal_sts_stage<T, 2>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
+    FUSCHK((with_kind<0, 1, 2>(pos, [&](auto K) -> int
+    {
+      hipLaunchKernelGGL((k_thermal_sts_stage<T, decltype(K)::value>), dim3(grid), dim3(256), 0, cx->stream, nvec, A);
+      return FUS_OK;
+    })));
     HIPCHK(hipGetLastError());
   }
   if (multi)
@@ -2430,12 +2318,11 @@ static int thermal_sts_end(fus_thermal* th, int j, double dt_, double sigma, con
     ProfScope ps(cx, "thermal_if");
     const dim3 gi(nblk(op->n_uidx)), blk(256);
     const T* recv = static_cast<const T*>(op->d_recvbuf);
-    if (j == 1)
-      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 0>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
-    else if (j < c.s)
-      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 1>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
-    else
-      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, 2>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+    FUSCHK((with_kind<0, 1, 2>(pos, [&](auto K) -> int
+    {
+      hipLaunchKernelGGL((k_thermal_if_sts_stage<T, decltype(K)::value>), gi, blk, 0, cx->stream, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc, recv, A);
+      return FUS_OK;
+    })));
     HIPCHK(hipGetLastError());
   }
   return FUS_OK;
@@ -3517,16 +3404,20 @@ static void layout_info(const Layout& L, size_t ts, int64_t out[8])
   out[7] = L.n_internal;
 }
 
-int fus_op_is_affine(fus_op* op) { return (op && op->affine) ? 1 : 0; }
-int fus_op_geometry_mode(fus_op* op) { return !op ? 0 : (op->affine ? 1 : (op->trilinear ? 2 : 0)); }
-int fus_op_uses_mfma(fus_op* op) { return (op && op->mfma) ? 1 : 0; }
-int fus_op_uses_diag_metric(fus_op* op) { return (op && op->diag) ? 1 : 0; }
+// which block kernel the operator runs, answered the way a launch decides it: the variant of the plain stiffness action
+static BlockVariant op_variant(const fus_op* op) { return block_variant(op->facts, op->traits, OP_STIFFNESS, STAGE_NONE); }
+int fus_op_is_affine(fus_op* op) { return (op && op->facts.mode == GEOM_AFFINE) ? 1 : 0; }
+int fus_op_geometry_mode(fus_op* op) { return !op ? 0 : op->facts.mode; }
+int fus_op_uses_mfma(fus_op* op) { return (op && op_variant(op).mf) ? 1 : 0; }
+int fus_op_uses_diag_metric(fus_op* op) { return (op && op_variant(op).geom == GEOM_DIAG) ? 1 : 0; }
 int fus_op_uses_mfma4(fus_op* op)
 {
-  // kernels.hpp mf4_contract_b: N = 8, fp64, trilinear geometry kernel, scalar (not the opt-in 16x16x4) form
-  return (op && FUS_MF4 && op->P == 7 && op->dtype == FUS_F64 && op->tdim == 3 && op->trilinear && !op->mfma) ? 1 : 0;
+  if (!op)
+    return 0;
+  const BlockVariant v = op_variant(op);
+  return uses_mf4(op->N, (int)op->ts, v.geom, v.mf) ? 1 : 0;
 }
-int fus_op_uses_pack32(fus_op* op) { return (op && op->pk && !op->mfma) ? 1 : 0; }
+int fus_op_uses_pack32(fus_op* op) { return (op && op_variant(op).pk) ? 1 : 0; }
 
 int fus_op_info(fus_op* op, int64_t out[8])
 {
@@ -4199,7 +4090,6 @@ int fus_model_monitor_get(fus_model* m, int quantity, int k, void* out, int spac
 }
 
 // ---- bioheat (fusmi.h): the typed implementation sits with the monitor's, ahead of the C ABI ----
-#define FUS_TH_CALL(th, fn, ...) ((th)->op->dtype == FUS_F64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
 // FUS_ERR_STATE while sums over the sharers wait for fus_group_thermal_finish
 static int thermal_ready(const fus_thermal* th, const char* fn)
@@ -4275,7 +4165,7 @@ int fus_thermal_create(fus_ctx* c, fus_op* op, const void* conductivity, const v
   HIPCHK(hipSetDevice(c->device));
   std::unique_ptr<fus_thermal> th(new fus_thermal());
   th->ctx = c, th->op = op, th->t_base = t_base;
-  const int r = FUS_TH_CALL(th, thermal_setup, th.get(), conductivity, rho_c, perfusion);
+  const int r = FUS_BY_DTYPE(th->op->dtype, thermal_setup, th.get(), conductivity, rho_c, perfusion);
   if (r != FUS_OK)
   {
     for (void* q : th->allocs)
@@ -4310,7 +4200,7 @@ int fus_thermal_init(fus_thermal* th)
   for (void* v : {th->th0, th->ths, th->acc})
     HIPCHK(hipMemsetAsync(v, 0, n * th->op->ts, th->ctx->stream));
   HIPCHK(hipMemsetAsync(th->dose, 0, n * sizeof(double), th->ctx->stream));
-  FUSCHK(FUS_TH_CALL(th, thermal_impose_rise, th));
+  FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_impose_rise, th));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
   th->initialised = true;
   return FUS_OK;
@@ -4322,7 +4212,7 @@ int fus_thermal_set(fus_thermal* th, int which, const void* in, int space)
     return fail(FUS_ERR_ARG, "fus_thermal_set: null argument, which not FUS_TH_RISE | FUS_TH_DOSE, or bad space");
   FUSCHK(thermal_ready(th, "fus_thermal_set"));
   HIPCHK(hipSetDevice(th->ctx->device));
-  FUSCHK(FUS_TH_CALL(th, thermal_vec, th, which, const_cast<void*>(in), space, true));
+  FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_vec, th, which, const_cast<void*>(in), space, true));
   th->initialised = true;
   return FUS_OK;
 }
@@ -4332,7 +4222,7 @@ int fus_thermal_get(fus_thermal* th, int which, void* out, int space)
   if (!th || !out || which < FUS_TH_RISE || which > FUS_TH_HEAT || (space != FUS_HOST && space != FUS_DEVICE))
     return fail(FUS_ERR_ARG, "fus_thermal_get: null argument, which not FUS_TH_RISE | FUS_TH_DOSE | FUS_TH_HEAT, or bad space");
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_vec, th, which, out, space, false);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_vec, th, which, out, space, false);
 }
 
 int fus_thermal_set_heat(fus_thermal* th, const void* q, const void* q_coef, int space)
@@ -4340,7 +4230,7 @@ int fus_thermal_set_heat(fus_thermal* th, const void* q, const void* q_coef, int
   if (!th || (space != FUS_HOST && space != FUS_DEVICE))
     return fail(FUS_ERR_ARG, "fus_thermal_set_heat: null argument or bad space");
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_set_heat, th, q, q_coef, space);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_set_heat, th, q, q_coef, space);
 }
 
 int fus_thermal_set_heat_from_monitor(fus_thermal* th, fus_model* m, const void* absorption)
@@ -4356,7 +4246,7 @@ int fus_thermal_set_heat_from_monitor(fus_thermal* th, fus_model* m, const void*
   if (m->mon_n == 0)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the monitor has taken no sample yet");
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_heat_from_monitor, th, m, absorption);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_heat_from_monitor, th, m, absorption);
 }
 
 int fus_thermal_set_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm, const void* absorption)
@@ -4376,7 +4266,7 @@ int fus_thermal_set_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm
   if (nharm > m->mon_nharm)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor holds fewer harmonics than nharm asks for");
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_heat_from_harmonics, th, m, nharm, absorption);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_heat_from_harmonics, th, m, nharm, absorption);
 }
 
 int fus_thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
@@ -4387,7 +4277,7 @@ int fus_thermal_lambda_max(fus_thermal* th, int iters, double* lambda)
     return fail(FUS_ERR_ARG, "fus_thermal_lambda_max: iters must be at least 1");
   FUSCHK(thermal_single(th, "fus_thermal_lambda_max", "fus_group_thermal_lambda_max"));
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_lambda_max, &th, 1, iters, lambda);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_lambda_max, &th, 1, iters, lambda);
 }
 
 int fus_thermal_steps(fus_thermal* th, double dt, int64_t nsteps, double heat_scale)
@@ -4400,7 +4290,7 @@ int fus_thermal_steps(fus_thermal* th, double dt, int64_t nsteps, double heat_sc
     return fail(FUS_ERR_STATE, "fus_thermal_init (or fus_thermal_set) must be called before fus_thermal_steps");
   HIPCHK(hipSetDevice(th->ctx->device));
   for (int64_t s = 0; s < nsteps; ++s)
-    FUSCHK(FUS_TH_CALL(th, thermal_step, th, dt, heat_scale));
+    FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_step, th, dt, heat_scale));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
   return FUS_OK;
 }
@@ -4420,7 +4310,7 @@ int fus_thermal_steps_sts(fus_thermal* th, double dt, int64_t nsteps, double hea
   if (!th->f0)   // objects that never use the scheme keep their footprint
     FUSCHK(dalloc_bytes(th->allocs, &th->f0, th->op->L.n_internal * th->op->ts, true, th->ctx->stream));
   for (int64_t s = 0; s < nsteps; ++s)
-    FUSCHK(FUS_TH_CALL(th, thermal_step_sts, th, dt, heat_scale, coef));
+    FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_step_sts, th, dt, heat_scale, coef));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
   return FUS_OK;
 }
@@ -4450,18 +4340,18 @@ int fus_group_thermal_finish(fus_thermal** ths, int n)
     FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->mw; }));
     for (int i = 0; i < n; ++i)
     {
-      FUSCHK(FUS_TH_CALL(ths[i], thermal_setup_finish, ths[i]));
+      FUSCHK(FUS_BY_DTYPE(ths[i]->op->dtype, thermal_setup_finish, ths[i]));
       ths[i]->pending &= ~fus_thermal::PEND_SETUP;
     }
   }
   if (any & fus_thermal::PEND_BC)   // one member's new boundary may fix DOFs of the others: all agree again
-    FUSCHK(FUS_TH_CALL(ths[0], thermal_agree_boundary, ths, n));
+    FUSCHK(FUS_BY_DTYPE(ths[0]->op->dtype, thermal_agree_boundary, ths, n));
   if (any & fus_thermal::PEND_HEAT)
   {
     FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->mq; }));
     for (int i = 0; i < n; ++i)
     {
-      FUSCHK(FUS_TH_CALL(ths[i], thermal_heat_finish, ths[i]));
+      FUSCHK(FUS_BY_DTYPE(ths[i]->op->dtype, thermal_heat_finish, ths[i]));
       ths[i]->pending &= ~fus_thermal::PEND_HEAT;
     }
   }
@@ -4497,15 +4387,15 @@ int fus_group_thermal_steps(fus_thermal** ths, int n, double dt, int64_t nsteps,
     for (int st = 0; st < (stages == 0 ? 4 : stages); ++st)
     {
       for (int i = 0; i < n; ++i)
-        FUSCHK(stages == 0 ? FUS_TH_CALL(ths[i], thermal_rk4_begin, ths[i], st) : FUS_TH_CALL(ths[i], thermal_sts_begin, ths[i], st + 1));
+        FUSCHK(stages == 0 ? FUS_BY_DTYPE(ths[i]->op->dtype, thermal_rk4_begin, ths[i], st) : FUS_BY_DTYPE(ths[i]->op->dtype, thermal_sts_begin, ths[i], st + 1));
       FUSCHK(halo_exchange_local(ops.data(), n));
       for (int i = 0; i < n; ++i)
-        FUSCHK(stages == 0 ? FUS_TH_CALL(ths[i], thermal_rk4_end, ths[i], st, dt, heat_scale)
-                           : FUS_TH_CALL(ths[i], thermal_sts_end, ths[i], st + 1, dt, heat_scale, coef));
+        FUSCHK(stages == 0 ? FUS_BY_DTYPE(ths[i]->op->dtype, thermal_rk4_end, ths[i], st, dt, heat_scale)
+                           : FUS_BY_DTYPE(ths[i]->op->dtype, thermal_sts_end, ths[i], st + 1, dt, heat_scale, coef));
     }
     if (stages != 0)
       for (int i = 0; i < n; ++i)
-        FUSCHK(FUS_TH_CALL(ths[i], thermal_sts_finish, ths[i]));
+        FUSCHK(FUS_BY_DTYPE(ths[i]->op->dtype, thermal_sts_finish, ths[i]));
   }
   for (int i = 0; i < n; ++i)
     HIPCHK(hipStreamSynchronize(ths[i]->ctx->stream));
@@ -4522,7 +4412,7 @@ static int thermal_group_lambda(fus_thermal** ths, int n, int iters, const char*
   for (int i = 0; i < n; ++i)
     FUSCHK(thermal_ready(ths[i], fn));
   HIPCHK(hipSetDevice(ths[0]->ctx->device));
-  return FUS_TH_CALL(ths[0], thermal_lambda_max, ths, n, iters, lambda);
+  return FUS_BY_DTYPE(ths[0]->op->dtype, thermal_lambda_max, ths, n, iters, lambda);
 }
 
 int fus_group_thermal_lambda_max(fus_thermal** ths, int n, int iters, double* lambda)
@@ -4554,7 +4444,7 @@ int fus_thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* 
   if (!th)
     return fail(FUS_ERR_ARG, "fus_thermal_set_boundary: null argument");
   HIPCHK(hipSetDevice(th->ctx->device));
-  return FUS_TH_CALL(th, thermal_set_boundary, th, fixed, fixed_rise, conv_diag, conv_rise);
+  return FUS_BY_DTYPE(th->op->dtype, thermal_set_boundary, th, fixed, fixed_rise, conv_diag, conv_rise);
 }
 
 int fus_thermal_boundary_info(fus_thermal* th, int64_t* nfixed, int64_t* nconvective)
@@ -4579,7 +4469,7 @@ int fus_thermal_stable_dt(fus_thermal* th, int iters, int stages, double* dt)
   FUSCHK(thermal_single(th, "fus_thermal_stable_dt", "fus_group_thermal_stable_dt"));
   HIPCHK(hipSetDevice(th->ctx->device));
   double rho = 0.0;
-  FUSCHK(FUS_TH_CALL(th, thermal_lambda_max, &th, 1, iters, &rho));
+  FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_lambda_max, &th, 1, iters, &rho));
   return thermal_dt_from("fus_thermal_stable_dt", rho, stages, dt);
 }
 

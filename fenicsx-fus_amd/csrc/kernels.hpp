@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_variant.hpp"
 #include "geom.hpp"
 #include "source_wave.hpp"
 
@@ -79,12 +80,8 @@ struct StageArgs
   const T* mn1;
 };
 
-enum
-{
-  STAGE_NONE = -1  // plain operator action: b / partial slab are written, no update
-};
-
-// Fused stage-update variants (template parameter STAGE of the block and shared-dof kernels).
+// Fused stage-update variants (template parameter STAGE of the block and shared-dof kernels; the kinds are named in
+// block_variant.hpp: STAGE_NONE = -1 is the plain operator action, b / partial slab are written, no update).
 //   0 first stage, 1 middle stage, 3 last stage of RK4: every stage keeps the accumulators u_, v_ in HBM
 //     the way Linear.hpp:282-294 does (used by the Runge-Kutta orders 1-3 and option "lean_rk4" = 0);
 //   4, 5, 6, 7 = stages 0-3 of the classical RK4 WITHOUT accumulators.  With V_0 = v0, U_0 = u0 and
@@ -170,12 +167,6 @@ __host__ __device__ inline int64_t g_index(int v, int p)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                         \
   } while (0)
 
-enum
-{
-  OP_STIFFNESS = 0,
-  OP_MASS = 1
-};
-
 // Phase timestamps of k_block_op exist in development builds only (build.py --dev -DFUS_TRACE pulls in
 // dev_trace.hpp); the product carries none.
 #ifdef FUS_TRACE
@@ -219,24 +210,7 @@ enum
 #ifndef FUS_HI_WAVES
 #define FUS_HI_WAVES 1
 #endif
-// Geometry source of the block operator
-//   GEOM_STREAM: per-point factors G / detJw streamed from HBM (any trilinear mesh; the reference's
-//                data path, precompute.hpp:101-213)
-//   GEOM_AFFINE: every cell is a parallelepiped (J constant per cell): 6 + 1 numbers per CELL,
-//                G(q) = Gc * w_q and detJw(q) = detc * w_q rebuilt in registers
-//   GEOM_TRILINEAR: any first-order hexahedron: 21 numbers per CELL (the coefficients of the trilinear
-//                map without its constant), J(q) and from it G(q) / detJw(q) recomputed per point
-//                in registers (the formulas of geom.hpp); trades the 6 N^3 streamed numbers per
-//                cell for ~65 flops per point
-enum
-{
-  GEOM_STREAM = 0,
-  GEOM_AFFINE = 1,
-  GEOM_TRILINEAR = 2,
-  // GEOM_AFFINE data on cells with mutually orthogonal edges (J^T J diagonal): the stiffness action in its
-  // diagonal-metric form (elem_compute); everything else as GEOM_AFFINE
-  GEOM_DIAG = 3
-};
+// (the geometry sources GEOM_STREAM / GEOM_AFFINE / GEOM_TRILINEAR / GEOM_DIAG of the block operator: block_variant.hpp)
 __host__ __device__ constexpr bool is_aff(int geom) { return geom == GEOM_AFFINE || geom == GEOM_DIAG; }
 
 template <typename T>
@@ -587,9 +561,7 @@ __host__ __device__ constexpr bool use_dpp4(int N, int geom)
 // parity's values come from lane ^ 8 (DPP row_ror:8), and the result D (row i = q >> 1 of parity beta) lands in lane
 // (q, c): no exchange tile, no wave barrier.  out(q, c) = sum_b M[q][b] in(b, c) with
 //   a_own = M[2 i + beta][2 k + beta],  a_swp = M[2 i + beta][2 k + 1 - beta]   (i = lane & 3, k = lane >> 4).
-#ifndef FUS_MF4
-#define FUS_MF4 1
-#endif
+// (where it is used: uses_mf4, block_variant.hpp)
 __device__ __forceinline__ double mf4_contract_b(double a_own, double a_swp, double v)
 {
   const double w = dpp_read<0x128>(v);   // the value of lane ^ 8: the other parity of b
@@ -876,7 +848,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       constexpr bool SWZ = (N == 8) && FUS_SWZ8;   // index-2 contractions by ds_swizzle instead of the tile (A/B)
       // index-1 contractions on the matrix cores (mf4_contract_b): the trilinear kernel, where it measured +5 ... +7 %
       // (the general affine kernel and the diagonal-metric form were even: profiles/r03_experiments.md section 6)
-      constexpr bool MF4 = (N == 8) && sizeof(T) == 8 && FUS_MF4 && GEOM == GEOM_TRILINEAR;
+      constexpr bool MF4 = uses_mf4(N, sizeof(T), GEOM, 0);
       T Tb[N], Uc[N], swc[8], swt[8];
       T mf_own = T(0), mf_swp = T(0), mt_own = T(0), mt_swp = T(0);
       if constexpr (MF4)
