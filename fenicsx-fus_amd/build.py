@@ -8,8 +8,8 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("fusmi.hip", "layout.cpp")]
-DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("kernels.hpp", "block_variant.hpp", "layout.hpp", "tables.hpp", "geom.hpp", "source_wave.hpp", "sts_coef.hpp", "thermal_bc.hpp", "thermal_owner.hpp")] + [
+SRC = [os.path.join(HERE, "csrc", f) for f in ("fusmi.hip", "layout.cpp", "degree_unit.hip")]
+DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("host.hpp", "kernels.hpp", "block_variant.hpp", "layout.hpp", "tables.hpp", "geom.hpp", "source_wave.hpp", "sts_coef.hpp", "thermal_bc.hpp", "thermal_owner.hpp")] + [
     os.path.join(HERE, "..", "include", "fusmi.h")]
 OUT = os.path.join(HERE, "fenicsxfus_amd", "libfusmi.so")
 
@@ -20,8 +20,8 @@ DEGREES = (2, 3, 4, 5, 6, 7, 8, 9, 10)
 
 
 def _compile_units(objdir, degrees, extra, verbose):
-    """fusmi.hip is compiled once per polynomial degree and scalar type (-DFUS_TU_DEGREE=k -DFUS_TU_DTYPE=64|32:
-    the block kernels of that degree) and once as the main unit (C ABI + degree-independent code), concurrently."""
+    """degree_unit.hip is compiled once per polynomial degree and scalar type (-DFUS_TU_DEGREE=k -DFUS_TU_DTYPE=64|32:
+    the block and geometry kernels of that degree) and fusmi.hip once (C ABI + all other code), concurrently."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -31,7 +31,7 @@ def _compile_units(objdir, degrees, extra, verbose):
             ([hipcc, *FLAGS, *extra, "-c", SRC[1], "-o", os.path.join(objdir, "layout.o")])]
     for k in degrees:
         for bits in (64, 32):
-            jobs.append([hipcc, *FLAGS, *extra, f"-DFUS_TU_DEGREE={k}", f"-DFUS_TU_DTYPE={bits}", "-c", SRC[0], "-o",
+            jobs.append([hipcc, *FLAGS, *extra, f"-DFUS_TU_DEGREE={k}", f"-DFUS_TU_DTYPE={bits}", "-c", SRC[2], "-o",
                          os.path.join(objdir, f"fusmi_p{k}_f{bits}.o")])
 
     def run(cmd):

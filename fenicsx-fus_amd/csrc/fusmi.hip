@@ -4,30 +4,16 @@
 // Reference counterparts: StiffnessSpectral3D / MassSpectral3D (spectral_op.hpp:29-107, 132-284),
 // LinearSpectral3D (Linear.hpp:52-347).  There is no CPU fallback in this file: every compute
 // entry point needs the HIP device and fails with FUS_ERR_HIP without one.
-#include "../../include/fusmi.h"
-
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <limits>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <type_traits>
-#include <utility>
+#include <limits>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "block_variant.hpp"
-#include "kernels.hpp"
-#include "layout.hpp"
+#include "host.hpp"
 #include "sts_coef.hpp"
 #include "thermal_bc.hpp"
 #include "thermal_owner.hpp"
@@ -35,43 +21,13 @@
 
 using namespace fus;
 
-// -------------------------------------------------------------------------------------------------
-// errors
-// -------------------------------------------------------------------------------------------------
-// One shared object is linked from several translation units of this file: the "main" unit (C ABI,
-// degree-independent code) and one unit per polynomial degree (-DFUS_TU_DEGREE=k) holding the
-// k_block_op instantiations of that degree, so that the degrees compile in parallel (build.py).
-#define FUS_HIDDEN __attribute__((visibility("hidden")))
-#ifdef FUS_TU_DEGREE
-extern FUS_HIDDEN thread_local std::string g_err;
-#else
-FUS_HIDDEN thread_local std::string g_err;
-#endif
-static int fail(int code, const std::string& msg)
-{
-  g_err = msg;
-  return code;
-}
-#define HIPCHK(expr)                                                                               \
-  do                                                                                               \
-  {                                                                                                \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(FUS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
+FUS_HIDDEN thread_local std::string g_err;   // the last error's text (fail, host.hpp), shared with the degree units
 #define NCCLCHK(expr)                                                                              \
   do                                                                                               \
   {                                                                                                \
     ncclResult_t r_ = (expr);                                                                      \
     if (r_ != ncclSuccess)                                                                         \
       return fail(FUS_ERR_RCCL, std::string(#expr) + ": " + g_rccl.GetErrorString(r_));            \
-  } while (0)
-#define FUSCHK(expr)                                                                               \
-  do                                                                                               \
-  {                                                                                                \
-    int r_ = (expr);                                                                               \
-    if (r_ != FUS_OK)                                                                              \
-      return r_;                                                                                   \
   } while (0)
 
 // -------------------------------------------------------------------------------------------------
@@ -92,9 +48,6 @@ struct RcclApi
   ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
   const char* (*GetErrorString)(ncclResult_t) = nullptr;
 };
-#ifdef FUS_TU_DEGREE
-extern FUS_HIDDEN RcclApi g_rccl;
-#else
 FUS_HIDDEN RcclApi g_rccl;
 
 static int rccl_load()
@@ -131,121 +84,10 @@ static int rccl_load()
   g_rccl = a;
   return FUS_OK;
 }
-#endif  // !FUS_TU_DEGREE
 
 // -------------------------------------------------------------------------------------------------
 // handles
 // -------------------------------------------------------------------------------------------------
-struct Prof
-{
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  double done_ms = 0;
-  int64_t done_count = 0;
-  int64_t seen = 0;   // scopes of this name since fus_profile_enable (level 2 samples every prof_sample-th)
-};
-
-struct fus_ctx
-{
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t comm_stream = nullptr;            // RCCL exchange, overlapped with local shared dofs
-  hipEvent_t ev_packed = nullptr, ev_recv = nullptr;
-  int deterministic = 0;  // 1: conflict-free rounds (bitwise reproducible); 0: LDS atomics
-  int fields = 1;         // operator inputs per block pass the ops are sized for (2: Lossy)
-  int graph = 0;          // 1: replay the RK step as one hipGraph (launch-bound sizes)
-  int geometry = 0;       // 0: auto (affine cells: 7 numbers per cell; other first-order hexahedra: the
-                          // cell's trilinear map, G recomputed per point; else streamed), 1: always
-                          // stream G, 2: as auto without the affine shortcut
-  // 0 = auto: 32 elements / 4 waves when G is streamed, 16 / 4 on the affine path (measured best
-  // on MI355X at p=4 fp64, profiles/r01_block_sweep.txt)
-  int block_elems = 0, waves = 0;
-  int prof = 0;  // 0 off, 1 all scopes, 2 block-operator kernel only
-  int prof_sample = 1;  // level 2: events around every prof_sample-th launch of the block-operator kernel (option "profile_sample")
-  std::map<std::string, Prof> profs;
-  ncclComm_t comm = nullptr;
-  int rank = 0, nranks = 1;
-  bool local_group = false;  // in-process transport (single-GPU rehearsal of the multi-rank path)
-  // timing rehearsal of the RCCL exchange on one GPU (option "halo_loopback"): the context keeps its
-  // logical (rank, nranks) but owns a 1-rank communicator and every send / receive goes to itself,
-  // so a middle slab exercises pack -> ncclSend/ncclRecv -> ordered unpack with realistic launch
-  // and synchronisation cost (the received planes are its own: results are NOT the physical ones)
-  bool loopback = false;
-  bool overlap_blocks = false;  // launch interface blocks first, overlap the exchange with the rest
-  bool external_transport = false;  // the caller exchanges the packed interface values (e.g. GPU-aware MPI)
-  int num_cus = 256;                // hipDeviceProp_t::multiProcessorCount
-  // Lossy / Westervelt boundary forms: 0 = the C++ benchmarks (BM7-SC1/forms.py:37-42: absorbing and
-  // delta-mass terms on every boundary facet, source doubled, Lossy.hpp:216-220); 1 = the Python
-  // package (python/src/fenicsxfus/_lossy.py:107-128, :186-189: those terms on tag 2 only, source
-  // not doubled)
-  int forms = 0;
-  // classical RK4 without the redundant accumulator streams (stage kinds 4-6, kernels.hpp): 1 (default);
-  // 0 keeps u_, v_ in HBM at every stage like Linear.hpp:282-294
-  int lean_rk4 = 1;
-  // index-1 / index-2 contractions of the degrees 6 and 7 on the matrix cores (per-cell geometry kernels):
-  // -1 auto (the measured choice per degree, scalar type and geometry), 0 never, 1 wherever a variant exists
-  int mfma = -1;
-  int pack32 = -1;  // fp32, degrees 5-7, per-cell geometry: two elements per wave in packed float2 (-1 auto, 0, 1)
-  // shared-dof stage kernel reads the partial sums as planes at the dof's own index (1, default) or through the
-  // shared-dof CSR (0; also taken when a dof has more than FUS_MAX_PLANES sharing blocks): same sums, same order
-  int planes = 1;
-  // affine meshes whose cells have mutually orthogonal edges (boxes): the stiffness action in its diagonal-metric
-  // form (three 1-D stiffness contractions, kernels.hpp elem_compute) -- 1 (default) where the mesh allows, 0 never
-  int diag_metric = 1;
-  int walk = 0;   // block-kernel workgroups per CU that walk several blocks each (0: one workgroup per block --
-                  // the measured best everywhere so far; -1: as many as are resident), see launch_block_op_v
-};
-
-struct Neigh
-{
-  int rank;
-  int64_t count;
-  int64_t off;  // first entry of this neighbour in the send / receive buffers
-};
-
-struct fus_op
-{
-  fus_ctx* ctx;
-  int P, N, Nd, dtype;
-  int tdim = 3;  // 3: hexahedra, 2: quadrilaterals (Nd = N^tdim)
-  size_t ts;  // sizeof(T)
-  int64_t ncells, ndofs, nnodes;
-  Layout L;
-  std::vector<double> nodes, wts, D;
-  std::vector<char> h_geom_x;        // caller geometry (host copy, T)
-  std::vector<int32_t> h_geom_dm;    // [ncells*geom_nv]
-  int geom_order = 1, geom_nv = 8;   // 1: 2^tdim vertices; 2: 27 nodes in tensor order (hexahedra)
-  std::vector<int32_t> h_dofmap;     // caller tensor dofmap
-  // device
-  BlockArgs A{};
-  std::vector<void*> allocs;
-  int32_t *d_cell_perm = nullptr, *d_dof_perm = nullptr;
-  int64_t *d_sh_ptr = nullptr, *d_sh_pairs = nullptr;
-  void *d_G = nullptr, *d_detJ = nullptr, *d_Dg = nullptr, *d_partial = nullptr;
-  void *d_tmp_x = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr, *d_tmp_coef = nullptr;
-  size_t lds_bytes = 0;
-  int deterministic = 0;
-  int nfields = 1;
-  // what decides the block kernel's variant (block_variant.hpp).  op_build fills both with the geometry mode it predicts
-  // (facts.mode; facts.ortho is found there); op_setup_device puts in the mode the device confirmed -- GEOM_AFFINE: per-cell
-  // factors in d_Gc, streamed G / detJ built only on demand; GEOM_TRILINEAR: d_Gc holds 21 map coefficients per cell --
-  // and settles traits.mfma and traits.diag; traits.pk stays what the layout was built with
-  OpFacts facts{};
-  OpTraits traits{};
-  void* d_Gc = nullptr;
-  void *d_xg = nullptr, *d_pts = nullptr, *d_wts = nullptr;
-  int32_t* d_xdm = nullptr;
-  // neighbours (multi-GPU)
-  std::vector<Neigh> neigh;
-  // halo buffers: concatenated neighbour lists (ascending rank), one send and one receive buffer;
-  // unique interface dofs with, per dof, its addends in ascending rank order (-1 = own partial)
-  int64_t n_halo = 0, n_uidx = 0;
-  int32_t *d_pack_idx = nullptr, *d_uidx = nullptr, *d_uptr = nullptr, *d_usrc = nullptr;
-  void *d_sendbuf = nullptr, *d_recvbuf = nullptr;
-  // the pseudo partial slots (next-stage boundary terms of shared boundary dofs) live in d_partial,
-  // i.e. per op, while several models may share one op: the model that wrote them last
-  const struct fus_model* bnd_owner = nullptr;
-};
-
 struct fus_model
 {
   fus_ctx* ctx;
@@ -341,24 +183,6 @@ static int upload(std::vector<void*>& pool, U** p, const std::vector<U>& v, hipS
     HIPCHK(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, st));
   return FUS_OK;
 }
-static inline unsigned nblk(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
-// A run-time integer as a template argument: f(std::integral_constant<int, K>{}) for the K of the list that equals
-// `kind`; f returns a status.  A kind outside the list is an error, never some other kernel.
-template <int... Ks, typename F>
-static int with_kind(int kind, F&& f)
-{
-  int r = FUS_OK;
-  if (((kind == Ks && ((r = f(std::integral_constant<int, Ks>{})), true)) || ...))
-    return r;
-  return fail(FUS_ERR_STATE, "no kernel variant of kind " + std::to_string(kind));
-}
-template <typename F, int... Ks>
-static int with_kind(int kind, F&& f, std::integer_sequence<int, Ks...>)
-{
-  return with_kind<Ks...>(kind, f);
-}
-
 // fn<double>(...) or fn<float>(...) by a FUS_F64 / FUS_F32 scalar type
 #define FUS_BY_DTYPE(dtype, fn, ...) ((dtype) == FUS_F64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
@@ -394,113 +218,6 @@ struct ProfScope
 // -------------------------------------------------------------------------------------------------
 // typed implementation
 // -------------------------------------------------------------------------------------------------
-template <typename T, int P, int OP, int ATOMIC, int STAGE, int NF, int GEOM, int TD = 3, int MF = 0, int PK = 0>
-static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x, T* bvec,
-                             const StageArgs<T>& S, int blk_begin, int blk_count)
-{
-  if (blk_count <= 0)
-    return FUS_OK;
-  constexpr int N = P + 1;
-  KArgs<T, N> K;
-  for (int i = 0; i < N * N; ++i)
-    K.Dk.d[i] = (T)op->D[i], K.Dk.dt[i] = (T)op->D[(i % N) * N + i / N];
-
-  for (int i = 0; i < N; ++i)
-    K.Dk.w[i] = (T)op->wts[i], K.Dk.x[i] = (T)op->nodes[i];
-  // the attribute is per device: one bit per device and instantiation (set again harmlessly if two
-  // threads race on the first launch)
-  static std::atomic<uint64_t> attr_set{0};
-  const uint64_t dev_bit = 1ull << (op->ctx->device & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit))
-  {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
-  K.A = op->A;
-  if (GEOM == GEOM_DIAG)
-  {
-    // the 1-D stiffness matrix K1 = D^T diag(w) D takes the derivative table's place (symmetric: d = dt)
-    for (int q = 0; q < N; ++q)
-      for (int i = 0; i < N; ++i)
-      {
-        double acc = 0;
-        for (int m = 0; m < N; ++m)
-          acc += op->D[m * N + q] * op->wts[m] * op->D[m * N + i];
-        K.Dk.d[q * N + i] = K.Dk.dt[q * N + i] = (T)acc;
-      }
-  }
-  K.A.blk_begin = blk_begin;
-  K.A.blk_count = blk_count;
-  K.Dg = static_cast<const T*>(op->d_Dg), K.geo = geo, K.coef = coef, K.x = x, K.bvec = bvec;
-  K.partial = static_cast<T*>(op->d_partial);
-  K.S = S;
-  // option "walk" = w > 0: w workgroups per CU, each walking every (w * CUs)-th block of the range with
-  // the next block's prologue loads in flight under the current block's epilogue (per-cell geometry
-  // kernels; the streamed-geometry kernel keeps one workgroup per block).  Off by default: measured on
-  // MI355X (config 2, profiles/r02_experiments.md) one workgroup per block is 13-17 % faster -- the
-  // hardware's own dispatch of a fresh workgroup into a freed slot overlaps the phases of different
-  // blocks better than the walking workgroup's software pipeline does.
-  int grid = blk_count;
-  if (GEOM != GEOM_STREAM && TD == 3 && op->ctx->walk != 0)
-  {
-    int per_cu = op->ctx->walk;
-    if (per_cu < 0)  // as many workgroups per CU as are resident at once, where each then has >= 4 blocks to walk
-    {
-      // resident workgroups per CU of this instantiation, per (device, waves per workgroup, LDS bytes)
-      static std::mutex occ_mu;
-      static std::map<std::tuple<int, int, size_t>, int> occ_cache;
-      int occ = 0;
-      {
-        std::lock_guard<std::mutex> lk(occ_mu);
-        const auto key = std::make_tuple(op->ctx->device, op->L.waves, op->lds_bytes);
-        auto it = occ_cache.find(key);
-        if (it == occ_cache.end())
-        {
-          int nb = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &nb, reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>), 64 * op->L.waves,
-              op->lds_bytes));
-          it = occ_cache.emplace(key, std::max(nb, 1)).first;
-        }
-        occ = it->second;
-      }
-      per_cu = (blk_count >= 4 * occ * op->ctx->num_cus) ? occ : 0;
-    }
-    if (per_cu > 0)
-      grid = std::min(blk_count, per_cu * op->ctx->num_cus);
-  }
-  hipLaunchKernelGGL((k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>), dim3(grid),
-                     dim3(64 * op->L.waves), op->lds_bytes, op->ctx->stream, K);
-  HIPCHK(hipGetLastError());
-  return FUS_OK;
-}
-
-// Blocks [blk_begin, blk_begin + blk_count) of the layout; blk_count < 0: all blocks.
-template <typename T, int P, int OP, int STAGE, int NF = 1>
-static int launch_block_op(fus_op* op, const T* geo, const T* coef, const T* x, T* bvec,
-                           const StageArgs<T>& S, int blk_begin = 0, int blk_count = -1)
-{
-  if (NF > op->nfields)
-    return fail(FUS_ERR_STATE, "operator data was not created for two-field models (option fields=2)");
-  if (blk_count < 0)
-    blk_count = op->L.nblocks - blk_begin;
-  // which kernel (block_variant.hpp), then the five integers as template arguments: of the keys only those whose
-  // kernel exists for <T, P, OP, STAGE> are compiled in
-  const BlockVariant v = block_variant(op->facts, op->traits, OP, STAGE);
-  const T* g = v.geom == GEOM_STREAM ? geo : static_cast<const T*>(op->d_Gc);   // streamed per-point arrays or per-cell factors
-  constexpr int NO_KERNEL = std::numeric_limits<int>::min();
-  const int r = with_kind(block_variant_key(v), [&](auto K) -> int
-  {
-    constexpr BlockVariant V = block_variant_of_key(decltype(K)::value);
-    if constexpr (block_variant_exists(P, sizeof(T), OP, STAGE, V))
-      return launch_block_op_v<T, P, OP, V.atomic, STAGE, NF, V.geom, V.td, V.mf, V.pk>(op, g, coef, x, bvec, S, blk_begin, blk_count);
-    else
-      return NO_KERNEL;
-  }, std::make_integer_sequence<int, block_variant_nkeys>{});
-  return r != NO_KERNEL ? r : fail(FUS_ERR_STATE, "this library holds no block kernel for the variant asked for");
-}
-
 template <typename T>
 static int shared_reduce(fus_op* op, T* bvec)
 {
@@ -515,18 +232,23 @@ static int shared_reduce(fus_op* op, T* bvec)
   return FUS_OK;
 }
 
-// b_internal = A x_internal  (all dofs: interior written by the block kernel, shared reduced)
-template <typename T, int P, int OP>
-static int apply_internal(fus_op* op, const T* coef, const T* x, T* bvec)
+// The degree unit (degree_unit.hip, DegreeImpl in host.hpp) of a scalar type and degree, nullptr where the library holds
+// none.  op_setup_device refuses such an operator, so every later call finds its unit.  Defined with the dispatch below.
+static const DegreeImpl* degree_impl(int dtype, int P);
+
+// b_internal = A x_internal  (all dofs: interior written by the block kernel, shared reduced) on device vectors in
+// internal numbering, coef in internal cell order; kind = OP_STIFFNESS | OP_MASS
+template <typename T>
+static int apply_internal(fus_op* op, int kind, const void* coef, const void* x, void* bvec)
 {
   fus_ctx* c = op->ctx;
   {
-    ProfScope ps(c, OP == OP_STIFFNESS ? "stiffness" : "mass");
-    const T* geo = static_cast<const T*>(OP == OP_STIFFNESS ? op->d_G : op->d_detJ);
+    ProfScope ps(c, kind == OP_STIFFNESS ? "stiffness" : "mass");
+    const void* geo = kind == OP_STIFFNESS ? op->d_G : op->d_detJ;
     StageArgs<T> none{};
-    FUSCHK((launch_block_op<T, P, OP, STAGE_NONE>(op, geo, coef, x, bvec, none)));
+    FUSCHK(degree_impl(op->dtype, op->P)->block_op(op, kind, STAGE_NONE, 1, geo, coef, x, bvec, &none, 0, -1));
   }
-  return shared_reduce<T>(op, bvec);
+  return shared_reduce<T>(op, static_cast<T*>(bvec));
 }
 
 // Shared-DOF exchange of a partial-sum vector (replaces b->scatter_rev(std::plus) +
@@ -635,38 +357,16 @@ static int halo_exchange_local(fus_op** ops, int n)
 
 // Per-point geometry factors in the streaming layouts (precompute.hpp:101-213, 33-94), computed on
 // the device.  Built at setup for non-affine meshes, on demand (fus_op_get_geometry) otherwise.
-template <typename T, int P>
+template <typename T>
 static int ensure_stream_geometry(fus_op* op)
 {
-  constexpr int N = P + 1;
   if (op->d_G)
     return FUS_OK;
   hipStream_t st = op->ctx->stream;
   const int Nd = op->Nd, ng = op->tdim == 3 ? 6 : 3;
   FUSCHK(dalloc_bytes(op->allocs, &op->d_G, (size_t)op->ncells * ng * Nd * sizeof(T), false, st));
   FUSCHK(dalloc_bytes(op->allocs, &op->d_detJ, (size_t)op->ncells * Nd * sizeof(T), false, st));
-  if (op->tdim == 2 && op->geom_order == 1)
-    hipLaunchKernelGGL((k_geometry2d<T, N, 1>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_xg), op->d_xdm,
-                       static_cast<const double*>(op->d_pts), static_cast<const double*>(op->d_wts),
-                       static_cast<T*>(op->d_G), static_cast<T*>(op->d_detJ));
-  else if (op->tdim == 2)
-    hipLaunchKernelGGL((k_geometry2d<T, N, 2>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_xg), op->d_xdm,
-                       static_cast<const double*>(op->d_pts), static_cast<const double*>(op->d_wts),
-                       static_cast<T*>(op->d_G), static_cast<T*>(op->d_detJ));
-  else if (op->geom_order == 1)
-    hipLaunchKernelGGL((k_geometry<T, N, 1>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_xg), op->d_xdm,
-                       static_cast<const double*>(op->d_pts), static_cast<const double*>(op->d_wts),
-                       static_cast<T*>(op->d_G), static_cast<T*>(op->d_detJ));
-  else
-    hipLaunchKernelGGL((k_geometry<T, N, 2>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_xg), op->d_xdm,
-                       static_cast<const double*>(op->d_pts), static_cast<const double*>(op->d_wts),
-                       static_cast<T*>(op->d_G), static_cast<T*>(op->d_detJ));
-  HIPCHK(hipGetLastError());
-  return FUS_OK;
+  return degree_impl(op->dtype, op->P)->stream_geometry(op);
 }
 
 // The facts behind the block kernel's variant (block_variant.hpp) for geometry mode `mode`, with the options as the
@@ -677,10 +377,12 @@ static OpFacts op_facts(const fus_op* op, int mode, bool ortho, int deterministi
   return {op->P, (int)op->ts, op->tdim, op->geom_order, mode, ortho, deterministic != 0, c->mfma, c->pack32, c->diag_metric};
 }
 
-template <typename T, int P>
+template <typename T>
 static int op_setup_device(fus_op* op)
 {
-  constexpr int N = P + 1;
+  if (!degree_impl(op->dtype, op->P))
+    return fail(FUS_ERR_ARG, "unsupported polynomial degree (2..10)");
+  const int N = op->N;
   fus_ctx* c = op->ctx;
   hipStream_t st = c->stream;
   Layout& L = op->L;
@@ -785,7 +487,7 @@ static int op_setup_device(fus_op* op)
   if (op->traits.gcs)
     op->lds_bytes = L.lds_bytes(sizeof(T), op->nfields, op->traits.gcs);
   else
-    FUSCHK((ensure_stream_geometry<T, P>(op)));
+    FUSCHK(ensure_stream_geometry<T>(op));
 
   FUSCHK(dalloc_bytes(pool, &op->d_partial, (size_t)(L.n_partial + L.n_shared) * sizeof(T), true, st));
   FUSCHK(dalloc_bytes(pool, &op->d_tmp_x, (size_t)L.n_internal * sizeof(T), true, st));
@@ -797,8 +499,8 @@ static int op_setup_device(fus_op* op)
 }
 
 // y += A(coeffs) x with caller-numbered vectors (the reference operator call)
-template <typename T, int P, int OP>
-static int op_apply(fus_op* op, const void* x, const void* coeffs, void* y, int space)
+template <typename T>
+static int op_apply(fus_op* op, int kind, const void* x, const void* coeffs, void* y, int space)
 {
   fus_ctx* c = op->ctx;
   hipStream_t st = c->stream;
@@ -819,7 +521,7 @@ static int op_apply(fus_op* op, const void* x, const void* coeffs, void* y, int 
                      op->d_dof_perm, xc, xin);
   hipLaunchKernelGGL((k_cells_to_internal<T>), dim3(nblk(op->ncells)), dim3(256), 0, st, op->ncells,
                      op->d_cell_perm, cc, coef_i);
-  FUSCHK((apply_internal<T, P, OP>(op, coef_i, xin, bint)));
+  FUSCHK(apply_internal<T>(op, kind, coef_i, xin, bint));
   if (space == FUS_HOST)
   {
     HIPCHK(hipMemcpyAsync(tc, y, op->ndofs * sizeof(T), hipMemcpyHostToDevice, st));
@@ -835,12 +537,11 @@ static int op_apply(fus_op* op, const void* x, const void* coeffs, void* y, int 
   return FUS_OK;
 }
 
-template <typename T, int P>
+template <typename T>
 static int op_get_geometry(fus_op* op, void* G, void* detJ)
 {
-  constexpr int N = P + 1;
   hipStream_t st = op->ctx->stream;
-  FUSCHK((ensure_stream_geometry<T, P>(op)));
+  FUSCHK(ensure_stream_geometry<T>(op));
   const int Nd = op->Nd, ng = op->tdim == 3 ? 6 : 3;
   std::vector<void*> tmp;
   T *dG = nullptr, *dd = nullptr;
@@ -848,15 +549,7 @@ static int op_get_geometry(fus_op* op, void* G, void* detJ)
     FUSCHK(dalloc(tmp, &dG, (size_t)op->ncells * Nd * ng));
   if (detJ)
     FUSCHK(dalloc(tmp, &dd, (size_t)op->ncells * Nd));
-  if (op->tdim == 2)
-    hipLaunchKernelGGL((k_geometry_export2d<T, N>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_G),
-                       static_cast<const T*>(op->d_detJ), dG, dd);
-  else
-    hipLaunchKernelGGL((k_geometry_export<T, N>), dim3(nblk(op->ncells * Nd)), dim3(256), 0, st,
-                       op->ncells, op->d_cell_perm, static_cast<const T*>(op->d_G),
-                       static_cast<const T*>(op->d_detJ), dG, dd);
-  HIPCHK(hipGetLastError());
+  FUSCHK(degree_impl(op->dtype, op->P)->export_geometry(op, dG, dd));
   if (G)
     HIPCHK(hipMemcpyAsync(G, dG, (size_t)op->ncells * Nd * ng * sizeof(T), hipMemcpyDeviceToHost, st));
   if (detJ)
@@ -943,7 +636,7 @@ static void facet_diag_host(const fus_op* op, int64_t nfacets, const int32_t* fc
   }
 }
 
-template <typename T, int P>
+template <typename T>
 static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const void* delta0_,
                        const void* beta0_, int64_t nfacets, const int32_t* fc, const int32_t* fl,
                        const int32_t* ft)
@@ -988,7 +681,7 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
   // lumped mass, this rank's cells only: m = M(1/(rho c^2)) 1  (Linear.hpp:127-133)
   T* ones = static_cast<T*>(m->un);
   hipLaunchKernelGGL((k_fill<T>), dim3(1024), dim3(256), 0, st, n, ones, T(1));
-  FUSCHK((apply_internal<T, P, OP_MASS>(op, d_mcoef, ones, static_cast<T*>(m->m))));
+  FUSCHK(apply_internal<T>(op, OP_MASS, d_mcoef, ones, m->m));
   if (m->kind == FUS_WESTERVELT)
   {
     // diagonal of the nonlinear mass action: mn1 = M(-2 beta/(rho^2 c^4)) 1  (Westervelt.hpp:185,
@@ -1003,7 +696,7 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
     T* d_n1;
     FUSCHK(upload(pool, &d_n1, n1, st));
     FUSCHK(dalloc_bytes(pool, &m->mn1, n * sizeof(T), true, st));
-    FUSCHK((apply_internal<T, P, OP_MASS>(op, d_n1, ones, static_cast<T*>(m->mn1))));
+    FUSCHK(apply_internal<T>(op, OP_MASS, d_n1, ones, m->mn1));
   }
   HIPCHK(hipMemsetAsync(m->un, 0, n * sizeof(T), st));
 
@@ -1239,8 +932,7 @@ static int stage_kind(const fus_model* m, int i)
     return STAGE_FIRST;
   return (m->rk_order == 4 && i == 3) ? STAGE_LAST : STAGE_MID;
 }
-// every kind stage_kind returns: the instantiations of the stage kernels
-#define FUS_STAGE_KINDS STAGE_FIRST, STAGE_MID, STAGE_LAST, STAGE_LEAN0, STAGE_LEAN1, STAGE_LEAN2, STAGE_LEAN3
+// (every kind stage_kind returns is in FUS_STAGE_KINDS, host.hpp: the instantiations of the stage kernels)
 
 // The stage's velocity buffers as the fused updates name them.  Stage kinds 0, 1, 3: the model's own vn, v_, u_.
 // Lean RK4 (kinds 4-7): the three stage velocities V_1, V_2, V_3 rotate through those three buffers (A = vn, B = v_,
@@ -1312,7 +1004,7 @@ static int source_entries(fus_model* m, int64_t k0, int64_t k1, double tn)
 // Stage i, first half: the block kernel applies K(-1/rho) to u_stage and, for every block-interior
 // dof, finishes the stage right away (boundary terms, kv = b/m, axpys); shared dofs leave as partial
 // sums, are reduced into b's shared range, and the interface entries are packed for the exchange.
-template <typename T, int P>
+template <typename T>
 static int stage_begin(fus_model* m, int i, double t, double dt)
 {
   fus_op* op = m->op;
@@ -1321,19 +1013,11 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   StageArgs<T> S = stage_args<T>(m, i, stage_scalars<T>(m, i, t, dt));
   const T* vstage = i == 0 ? static_cast<const T*>(m->v0) : S.vn;   // the velocity this stage starts from
   S.x2 = vstage;   // lossy: second operator input v_n
-  const T* G = static_cast<const T*>(op->d_G);
-  const T* coef = static_cast<const T*>(m->coef);
   const int kind = stage_kind(m, i);
   const bool two_fields = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
+  const DegreeImpl* deg = degree_impl(op->dtype, op->P);
   auto launch = [&](int b0, int nb) -> int
-  {
-    return with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
-    {
-      constexpr int KIND = decltype(K)::value;
-      return two_fields ? launch_block_op<T, P, OP_STIFFNESS, KIND, 2>(op, G, coef, ustage, b, S, b0, nb)
-                        : launch_block_op<T, P, OP_STIFFNESS, KIND, 1>(op, G, coef, ustage, b, S, b0, nb);
-    });
-  };
+  { return deg->block_op(op, OP_STIFFNESS, kind, two_fields ? 2 : 1, op->d_G, m->coef, ustage, b, &S, b0, nb); };
   // Multi-rank, option "overlap_blocks": the blocks that touch interface dofs (first in the layout)
   // run ahead, their partials are reduced, packed and handed to the exchange, and the remaining
   // blocks (the bulk of the stage) run while the planes are in flight.  Off by default: the exchange
@@ -1493,12 +1177,12 @@ static int stage_end(fus_model* m, int i, double t, double dt)
 
 // One classical RK4 step (Linear.hpp:273-295), state in (u0, v0) on entry and exit; RCCL (or
 // single-rank) transport.
-template <typename T, int P>
+template <typename T>
 static int model_step(fus_model* m, double t, double dt)
 {
   for (int i = 0; i < m->rk_order; ++i)
   {
-    FUSCHK((stage_begin<T, P>(m, i, t, dt)));
+    FUSCHK(stage_begin<T>(m, i, t, dt));
     if (!m->op->neigh.empty())
     {
       ProfScope ps(m->ctx, "halo");
@@ -1543,66 +1227,14 @@ static int model_getset(fus_model* m, int which, void* host_or_dev, int space, b
 }
 
 // -------------------------------------------------------------------------------------------------
-// dispatch over (dtype, P): the degree-dependent entry points live in the per-degree units
+// dispatch over (dtype, P): the launches that hold the degree live in the per-degree units (degree_unit.hip)
 // -------------------------------------------------------------------------------------------------
-struct DegreeImpl
-{
-  int (*op_setup)(fus_op*);
-  int (*op_apply)(fus_op*, int, const void*, const void*, void*, int);
-  int (*op_get_geometry)(fus_op*, void*, void*);
-  int (*model_setup)(fus_model*, const void*, const void*, const void*, const void*, int64_t,
-                     const int32_t*, const int32_t*, const int32_t*);
-  int (*model_step)(fus_model*, double, double);
-  int (*stage_begin)(fus_model*, int, double, double);
-  // b = A(coef) x on device vectors in internal numbering, coef in internal cell order (apply_internal: the plain
-  // operator action op_apply runs, without its renumbering passes); kind = OP_STIFFNESS | OP_MASS
-  int (*apply_int)(fus_op*, int, const void*, const void*, void*);
-};
-#define FUS_CAT_(a, b) a##b
-#define FUS_CAT(a, b) FUS_CAT_(a, b)
-
-#ifdef FUS_TU_DEGREE
-template <typename T, int P>
-static int op_apply_kind(fus_op* op, int kind, const void* x, const void* cf, void* y, int space)
-{
-  return kind == OP_STIFFNESS ? op_apply<T, P, OP_STIFFNESS>(op, x, cf, y, space)
-                              : op_apply<T, P, OP_MASS>(op, x, cf, y, space);
-}
-template <typename T, int P>
-static int apply_int_kind(fus_op* op, int kind, const void* cf, const void* x, void* b)
-{
-  return kind == OP_STIFFNESS
-             ? apply_internal<T, P, OP_STIFFNESS>(op, static_cast<const T*>(cf), static_cast<const T*>(x), static_cast<T*>(b))
-             : apply_internal<T, P, OP_MASS>(op, static_cast<const T*>(cf), static_cast<const T*>(x), static_cast<T*>(b));
-}
-template <typename T, int P>
-static DegreeImpl make_degree_impl()
-{
-  return {&op_setup_device<T, P>, &op_apply_kind<T, P>, &op_get_geometry<T, P>,
-          &model_setup<T, P>,     &model_step<T, P>,    &stage_begin<T, P>,
-          &apply_int_kind<T, P>};
-}
-// one unit per (degree, scalar type): -DFUS_TU_DEGREE=k -DFUS_TU_DTYPE=64|32
-#if FUS_TU_DTYPE == 64
-FUS_HIDDEN const DegreeImpl* FUS_CAT(FUS_CAT(fus_degree_impl_, FUS_TU_DEGREE), _f64)()
-{
-  static const DegreeImpl d = make_degree_impl<double, FUS_TU_DEGREE>();
-  return &d;
-}
-#else
-FUS_HIDDEN const DegreeImpl* FUS_CAT(FUS_CAT(fus_degree_impl_, FUS_TU_DEGREE), _f32)()
-{
-  static const DegreeImpl d = make_degree_impl<float, FUS_TU_DEGREE>();
-  return &d;
-}
-#endif
-#else  // main unit: everything from here to the end of the file
 #define FUS_DECL_DEGREE(k)                                                                         \
-  FUS_HIDDEN const DegreeImpl* FUS_CAT(FUS_CAT(fus_degree_impl_, k), _f64)();                      \
-  FUS_HIDDEN const DegreeImpl* FUS_CAT(FUS_CAT(fus_degree_impl_, k), _f32)();
+  FUS_HIDDEN const DegreeImpl* FUS_DEGREE_IMPL_FN(k, 64)();                                        \
+  FUS_HIDDEN const DegreeImpl* FUS_DEGREE_IMPL_FN(k, 32)();
 #define FUS_CASE_DEGREE(k)                                                                         \
   case k:                                                                                          \
-    return dtype == FUS_F64 ? FUS_CAT(FUS_CAT(fus_degree_impl_, k), _f64)() : FUS_CAT(FUS_CAT(fus_degree_impl_, k), _f32)();
+    return dtype == FUS_F64 ? FUS_DEGREE_IMPL_FN(k, 64)() : FUS_DEGREE_IMPL_FN(k, 32)();
 #ifdef FUS_DEV_BUILD  // developer iteration build: ONE degree (never shipped; build.py --dev)
 #ifndef FUS_DEV_DEGREE
 #define FUS_DEV_DEGREE 4
@@ -1629,38 +1261,7 @@ static const DegreeImpl* degree_impl(int dtype, int P)
   }
 }
 #endif
-#define FUS_DEGREE(d, dtype_, P_)                                                                  \
-  const DegreeImpl* d = degree_impl(dtype_, P_);                                                   \
-  if (!d)                                                                                          \
-    return fail(FUS_ERR_ARG, "unsupported polynomial degree (2..10)");
 
-static int d_op_setup(fus_op* op)
-{
-  FUS_DEGREE(d, op->dtype, op->P);
-  return d->op_setup(op);
-}
-static int d_op_apply(fus_op* op, int kind, const void* x, const void* cf, void* y, int space)
-{
-  FUS_DEGREE(d, op->dtype, op->P);
-  return d->op_apply(op, kind, x, cf, y, space);
-}
-static int d_apply_int(fus_op* op, int kind, const void* cf, const void* x, void* b)
-{
-  FUS_DEGREE(d, op->dtype, op->P);
-  return d->apply_int(op, kind, cf, x, b);
-}
-static int d_op_get_geometry(fus_op* op, void* G, void* dJ)
-{
-  FUS_DEGREE(d, op->dtype, op->P);
-  return d->op_get_geometry(op, G, dJ);
-}
-static int d_model_setup(fus_model* m, const void* c0, const void* rho0, const void* delta0,
-                         const void* beta0, int64_t nf, const int32_t* fc, const int32_t* fl,
-                         const int32_t* ft)
-{
-  FUS_DEGREE(d, m->op->dtype, m->op->P);
-  return d->model_setup(m, c0, rho0, delta0, beta0, nf, fc, fl, ft);
-}
 // One RK step.  Option "graph" (one rank, no per-kernel events): the step's launches are captured
 // into a graph and replayed as ONE submission -- for launch-bound sizes (BASELINE config 1: eight
 // kernels of a few microseconds).  The stage scalars (source value at the stage times) are kernel
@@ -1669,14 +1270,13 @@ static int d_model_setup(fus_model* m, const void* c0, const void* rho0, const v
 // (it has one more launch, k_boundary_partial, and sets the kernels' attributes).
 static int d_model_step(fus_model* m, double t, double dt)
 {
-  FUS_DEGREE(d, m->op->dtype, m->op->P);
   fus_ctx* c = m->ctx;
   const bool graphed = c->graph && c->nranks <= 1 && !c->prof && m->op->neigh.empty() && m->gsteps > 0;
   ++m->gsteps;
   if (!graphed)
-    return d->model_step(m, t, dt);
+    return FUS_BY_DTYPE(m->op->dtype, model_step, m, t, dt);
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  const int r = d->model_step(m, t, dt);
+  const int r = FUS_BY_DTYPE(m->op->dtype, model_step, m, t, dt);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(c->stream, &g);
   if (r != FUS_OK || e != hipSuccess || !g)
@@ -1711,11 +1311,6 @@ static int d_model_step(fus_model* m, double t, double dt)
   if (el != hipSuccess)
     return fail(FUS_ERR_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(el));
   return FUS_OK;
-}
-static int d_stage_begin(fus_model* m, int i, double t, double dt)
-{
-  FUS_DEGREE(d, m->op->dtype, m->op->P);
-  return d->stage_begin(m, i, t, dt);
 }
 static int d_stage_end(fus_model* m, int i, double t, double dt) { return FUS_BY_DTYPE(m->op->dtype, stage_end, m, i, t, dt); }
 static int d_setup_finish(fus_model* m) { return FUS_BY_DTYPE(m->op->dtype, model_setup_finish, m); }
@@ -1815,7 +1410,7 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
         return fail(FUS_ERR_LIMIT, "a one-element block does not fit the LDS budget at this degree");
       break;
     }
-    int r8 = d_op_setup(op);
+    int r8 = FUS_BY_DTYPE(op->dtype, op_setup_device, op);
     if (r8 != FUS_OK)
     {
       for (void* q : op->allocs)
@@ -1883,7 +1478,7 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
       return fail(FUS_ERR_LIMIT, "a one-element block does not fit the LDS budget at this degree");
     break;
   }
-  int r = d_op_setup(op);
+  int r = FUS_BY_DTYPE(op->dtype, op_setup_device, op);
   if (r != FUS_OK)
   {
     for (void* q : op->allocs)
@@ -2090,7 +1685,7 @@ static int thermal_lumped(fus_thermal* th, const T* coef_i, T* out)
   const int64_t n = op->L.n_internal;
   hipLaunchKernelGGL((k_fill<T>), dim3(1024), dim3(256), 0, st, n, static_cast<T*>(th->acc), T(1));
   HIPCHK(hipMemsetAsync(out, 0, n * sizeof(T), st));
-  FUSCHK(d_apply_int(op, OP_MASS, coef_i, th->acc, out));
+  FUSCHK(FUS_BY_DTYPE(op->dtype, apply_internal, op, OP_MASS, coef_i, th->acc, out));
   HIPCHK(hipMemsetAsync(th->acc, 0, n * sizeof(T), st));
   return FUS_OK;
 }
@@ -2172,7 +1767,7 @@ static unsigned thermal_grid(const fus_thermal* th, int64_t* nvec, bool local = 
 template <typename T>
 static int thermal_stage_begin(fus_thermal* th, const T* x)
 {
-  FUSCHK(d_apply_int(th->op, OP_STIFFNESS, th->kneg, x, th->b));
+  FUSCHK(FUS_BY_DTYPE(th->op->dtype, apply_internal, th->op, OP_STIFFNESS, th->kneg, x, th->b));
   FUSCHK(thermal_robin<T>(th, x, true));
   if (thermal_multi(th))
   {
@@ -2645,7 +2240,7 @@ static int thermal_lambda_max(fus_thermal** ths, int n, int iters, double* lambd
     for (int i = 0; i < n; ++i)
     {
       fus_thermal* th = ths[i];
-      FUSCHK(d_apply_int(th->op, OP_STIFFNESS, th->kneg, th->ths, th->b));
+      FUSCHK(FUS_BY_DTYPE(th->op->dtype, apply_internal, th->op, OP_STIFFNESS, th->kneg, th->ths, th->b));
       FUSCHK(thermal_robin<T>(th, static_cast<const T*>(th->ths), false));
     }
     FUSCHK(thermal_sum(ths, n, [](fus_thermal* t) -> void* { return t->b; }));
@@ -3336,7 +2931,7 @@ int fus_stiffness_apply(fus_op* op, const void* x, const void* coeffs, void* y, 
   if (!op || !x || !coeffs || !y)
     return fail(FUS_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(op->ctx->device));
-  return d_op_apply(op, OP_STIFFNESS, x, coeffs, y, space);
+  return FUS_BY_DTYPE(op->dtype, op_apply, op, OP_STIFFNESS, x, coeffs, y, space);
 }
 
 int fus_mass_apply(fus_op* op, const void* x, const void* coeffs, void* y, int space)
@@ -3344,7 +2939,7 @@ int fus_mass_apply(fus_op* op, const void* x, const void* coeffs, void* y, int s
   if (!op || !x || !coeffs || !y)
     return fail(FUS_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(op->ctx->device));
-  return d_op_apply(op, OP_MASS, x, coeffs, y, space);
+  return FUS_BY_DTYPE(op->dtype, op_apply, op, OP_MASS, x, coeffs, y, space);
 }
 
 // sum over the LOCAL cells of the GLL-quadrature integral of x^2 (= x . M(1) x with the local,
@@ -3382,7 +2977,7 @@ int fus_op_get_geometry(fus_op* op, void* G, void* detJ)
   if (!op)
     return fail(FUS_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(op->ctx->device));
-  return d_op_get_geometry(op, G, detJ);
+  return FUS_BY_DTYPE(op->dtype, op_get_geometry, op, G, detJ);
 }
 
 int fus_op_get_tables(fus_op* op, double* weights, double* dphi)
@@ -3589,7 +3184,7 @@ int fus_model_create(fus_ctx* c, int kind, fus_op* op, const void* c0, const voi
   m->ctx = c, m->op = op, m->kind = kind, m->freq = freq, m->amp = amp, m->speed = speed;
   m->forms = c->forms;
   m->lean_rk4 = c->lean_rk4;
-  int r = d_model_setup(m.get(), c0, rho0, delta0, beta0, nfacets, facet_cells, facet_local, facet_tags);
+  int r = FUS_BY_DTYPE(op->dtype, model_setup, m.get(), c0, rho0, delta0, beta0, nfacets, facet_cells, facet_local, facet_tags);
   if (r == FUS_OK && !c->local_group)
   {
     // add the sharers' parts of the lumped mass over RCCL, then finish; with the in-process
@@ -3670,7 +3265,7 @@ int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nst
     for (int st = 0; st < ms[0]->rk_order; ++st)
     {
       for (int i = 0; i < n; ++i)
-        FUSCHK(d_stage_begin(ms[i], st, t, dt));   // includes the pack
+        FUSCHK(FUS_BY_DTYPE(ms[i]->op->dtype, stage_begin, ms[i], st, t, dt));   // includes the pack
       std::vector<fus_op*> ops(n);
       for (int i = 0; i < n; ++i)
         ops[i] = ms[i]->op;
@@ -3767,7 +3362,7 @@ int fus_model_stage_begin(fus_model* m, int stage, double t, double dt)
     return fail(FUS_ERR_STATE, "fus_model_setup_finish and fus_model_init come first");
   if (stage < 0 || stage >= m->rk_order)
     return fail(FUS_ERR_ARG, "stage out of range");
-  FUSCHK(d_stage_begin(m, stage, t, dt));
+  FUSCHK(FUS_BY_DTYPE(m->op->dtype, stage_begin, m, stage, t, dt));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));   // the send buffer is complete on return
   return FUS_OK;
 }
@@ -4671,18 +4266,3 @@ int fus_profile_get(fus_ctx* c, const char* name, double* total_ms, int64_t* cou
 }
 
 } // extern "C"
-#endif  // !FUS_TU_DEGREE
-
-#ifndef FUS_TRACE_BITS
-#define FUS_TRACE_BITS 64   // scalar type whose unit exports the trace (-DFUS_TRACE_BITS=32 for the fp32 kernels)
-#endif
-#if defined(FUS_TRACE) && defined(FUS_TU_DEGREE) && FUS_TU_DTYPE == FUS_TRACE_BITS
-// experiment builds: phase timestamps of the last k_block_op launch of this degree's unit
-extern "C" int fus_debug_trace(unsigned long long* out, long long nblocks)
-{
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(fus::g_fus_trace), (size_t)nblocks * 8 * sizeof(unsigned long long))
-                 == hipSuccess
-             ? 0
-             : -2;
-}
-#endif

@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage: tools/regs.sh DEGREE GEOM [extra -D flags]  -- VGPR / scratch of the k_block_op variants of one degree
+# (the fp64 unit; -DFUS_TU_DTYPE=32 among the extra flags: the fp32 one)
 deg=$1; geom=$2; shift; shift
-mkdir -p /tmp/regchk && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -DFUS_DEV_BUILD -DFUS_DEV_DEGREE=$deg -DFUS_TU_DEGREE=$deg "$@" --cuda-device-only -S $(dirname $0)/../fenicsx-fus_amd/csrc/fusmi.hip -o /tmp/regchk/p.s 2>/dev/null
+mkdir -p /tmp/regchk && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -DFUS_TU_DEGREE=$deg -DFUS_TU_DTYPE=64 "$@" --cuda-device-only -S $(dirname $0)/../fenicsx-fus_amd/csrc/degree_unit.hip -o /tmp/regchk/p.s 2>/dev/null
 python3 - $geom <<'PY'
 import re,sys
 s=open('/tmp/regchk/p.s').read()
