@@ -1,6 +1,7 @@
-// host.hpp -- what the two kinds of translation unit of libfusmi share on the host: fusmi.hip (the C ABI and all
-// orchestration, compiled once) and degree_unit.hip (compiled once per polynomial degree and scalar type, so that the
-// k_block_op instantiations of the degrees compile in parallel: build.py).  The seam between them is DegreeImpl below.
+// host.hpp -- what all translation units of libfusmi share on the host: the units compiled once (fusmi.hip: the
+// operator, the wave models, their C ABI and orchestration; the bioheat model's unit, which adds core.hpp) and
+// degree_unit.hip (compiled once per polynomial degree and scalar type, so that the k_block_op instantiations of the
+// degrees compile in parallel: build.py).  The seam between fusmi.hip and the degree units is DegreeImpl below.
 #ifndef FUS_HOST_HPP
 #define FUS_HOST_HPP
 

@@ -59,7 +59,7 @@ def polynomial(s, z):
 
 def step(bio, theta, dt, s, h=None, sigma=1.0):
     """One RKL2 step of thermal_ref.Bioheat ``bio``, in its scalar type T.  In float the stage scalars are rounded as
-    thermal_sts_end (fusmi.hip) rounds them: mu_j, nu_j, 1 - mu_j - nu_j, mut_j dt and gat_j dt are each formed in
+    thermal_sts_end (thermal.hip) rounds them: mu_j, nu_j, 1 - mu_j - nu_j, mut_j dt and gat_j dt are each formed in
     double and rounded to T once; in double the rounding changes nothing."""
     mu, nu, mut, gat = coefficients(s)
     T = bio.T

@@ -59,7 +59,7 @@ class BioheatBC(Bioheat):
         return np.where(self.fixed, 0.0, r / self.m_c)
 
     def finish_step(self, theta):
-        """Float: the library puts the fixed values back after every step (thermal_sts_finish: mu Y + nu Y + om Y
+        """Float: the library puts the fixed values back after every step (thermal_run, RKL2: mu Y + nu Y + om Y
         returns Y only up to rounding; RK4's stages add an exact zero there)."""
         return theta if self.exact else self.impose(theta)
 

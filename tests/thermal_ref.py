@@ -68,7 +68,7 @@ class Bioheat:
     """The discrete Pennes model on a Problem ``pr`` with per-cell k, rho_c, W (arrays or scalars), in ``pr``'s scalar
     type T.  In double it is the reference.  In float it is the plain sequential restatement of what the library computes
     (the yardstick of fp32_budget.py): K and M are the float oracle's, every vector is float32, and every scalar is
-    rounded where fusmi.hip rounds it -- dt to T first and then times T(a), T(b) (thermal_rk4_end), sigma to T, and the
+    rounded where thermal.hip rounds it -- dt to T first and then times T(a), T(b) (thermal_rk4_end), sigma to T, and the
     stage multiplies by the stored vector 1 / m_C (k_reciprocal) where the double reference divides by m_C."""
 
     def __init__(self, pr, k, rho_c, w=None):
