@@ -55,7 +55,8 @@ struct fus_model
   int32_t* d_rc_idx = nullptr;
   void *d_rc_bas = nullptr, *d_rc_out = nullptr, *d_rec = nullptr;
   int rec_every = 0, rec_which = 0;
-  int64_t rec_cap = 0, rec_n = 0, rec_step = 0;
+  int64_t rec_cap = 0, rec_n = 0, rec_step = 0;  // rec_cap: the records the last fus_model_record asked for
+  int64_t rec_alloc = 0;                         // records d_rec has room for (it only grows)
   std::vector<double> rec_times;
   // field monitor (fus_model_monitor): per-DOF accumulator planes over the internal vector, one allocation --
   // T[2][n_internal] (max, min) then double[2 + 2 nharm][n_internal] (sum, sum of squares, cos_k, sin_k)

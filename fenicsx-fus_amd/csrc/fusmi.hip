@@ -2239,8 +2239,12 @@ int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nst
   if (!ms || n < 1)
     return fail(FUS_ERR_ARG, "bad group");
   for (int i = 0; i < n; ++i)
-    if (!ms[i]->setup_done || !ms[i]->initialised)
+    if (!ms[i] || !ms[i]->setup_done || !ms[i]->initialised)
       return fail(FUS_ERR_STATE, "group member not set up / initialised");
+  // one stage loop steps every member: they must be the same scheme on the same model and scalar type
+  for (int i = 1; i < n; ++i)
+    if (ms[i]->rk_order != ms[0]->rk_order || ms[i]->kind != ms[0]->kind || ms[i]->op->dtype != ms[0]->op->dtype)
+      return fail(FUS_ERR_ARG, "group members differ in rk_order, model kind or scalar type");
   double t = t0;
   for (int64_t s = 0; s < nsteps; ++s)
   {
@@ -2487,7 +2491,7 @@ int fus_model_set_receivers(fus_model* m, int64_t npts, const int32_t* cells, co
   hipStream_t st = m->ctx->stream;
   HIPCHK(hipStreamSynchronize(st));
   m->rc_n = npts;
-  m->rec_every = 0, m->rec_n = 0, m->rec_cap = 0, m->rec_times.clear();
+  m->rec_every = 0, m->rec_n = 0, m->rec_cap = 0, m->rec_alloc = 0, m->rec_times.clear();
   FUSCHK(upload(m->allocs, &m->d_rc_idx, idx, st));
   if (op->dtype == FUS_F64)
   {
@@ -2532,10 +2536,14 @@ int fus_model_record(fus_model* m, int which, int every, int64_t capacity)
     return fail(FUS_ERR_STATE, "fus_model_set_receivers has not been called");
   HIPCHK(hipSetDevice(m->ctx->device));
   m->rec_every = every, m->rec_which = which, m->rec_n = 0, m->rec_step = 0, m->rec_times.clear();
-  if (every > 0 && capacity > m->rec_cap)
+  if (every > 0)
   {
-    FUSCHK(dalloc_bytes(m->allocs, &m->d_rec, (size_t)capacity * std::max<int64_t>(m->rc_n, 1) * m->op->ts, false, m->ctx->stream));
-    m->rec_cap = capacity;
+    if (capacity > m->rec_alloc)
+    {
+      FUSCHK(dalloc_bytes(m->allocs, &m->d_rec, (size_t)capacity * std::max<int64_t>(m->rc_n, 1) * m->op->ts, false, m->ctx->stream));
+      m->rec_alloc = capacity;
+    }
+    m->rec_cap = capacity;  // the limit of this recording, whatever an earlier one allocated
   }
   return FUS_OK;
 }

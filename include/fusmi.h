@@ -118,7 +118,8 @@ int fus_comm_allreduce(fus_ctx* ctx, double* values, int n, int op);
 /* In-process transport for rehearsing the multi-rank path on ONE GPU (tests): the n contexts of
  * this process become ranks 0..n-1 and interface planes move by device copies instead of RCCL.
  * Models of such contexts are finished with fus_group_finish_setup (the sharers' parts of m and
- * of the boundary weights) and advanced in lock-step with fus_group_rk4_steps. */
+ * of the boundary weights) and advanced in lock-step with fus_group_rk4_steps.  One stage loop steps every member,
+ * so the members of a group agree in rk_order, model kind and scalar type: otherwise FUS_ERR_ARG before any launch. */
 int fus_comm_init_local(fus_ctx** ctxs, int n);
 
 /* ---- operator data ------------------------------------------------------------------------
@@ -268,7 +269,8 @@ int64_t fus_model_ndofs(fus_model* model); /* number_of_dofs(), Linear.hpp:318 (
  * u_h (FUS_U) or v_h (FUS_V) at the receivers from the vectors resident in HBM -- no full-vector copy.
  *   fus_model_sample       T[npts] now, into host or device memory (`space`)
  *   fus_model_record       sample `which` after every `every`-th step into a device buffer of `capacity` records
- *                          (every = 0: off); restarts the record count.  A step is one of fus_model_rk4 /
+ *                          (every = 0: off); restarts the record count; `capacity` is the limit of this recording,
+ *                          whatever an earlier call asked for.  A step is one of fus_model_rk4 /
  *                          fus_model_rk4_steps, of fus_group_rk4_steps (every member records by itself) or, under the
  *                          external transport, the fus_model_stage_end of a step's last stage (time t + dt).  A rank
  *                          that holds none of the receivers (npts = 0) counts its records and their times all the same

@@ -7,7 +7,7 @@ import numpy as np
 import fenicsxfus_amd as fa
 from fenicsxfus_amd import tag_box_boundary
 from fp32_budget import promoted
-from util import Problem, layer_and_face_regions, live_state
+from util import Problem, layer_and_face_regions, live_state, slab_interface_regions
 
 F0, S0 = 0.5e6, 1500.0
 TOL_RK = 1e-10
@@ -74,7 +74,7 @@ class Case:
     def vectors(self, pr, change=None, eps=1e-6, scale_far_corner=None):
         """The oracle's model vectors on ``pr``; ``change`` scales one of them by 1 + eps:
         "absb_far" the absorbing weight on the far face x = L, "coef_last" the stiffness coefficient of the last
-        element layer along x."""
+        element layer along x, ("mass", DOF mask) the lumped mass on those DOFs."""
         c, rho, delta, beta = self.materials(scale_far_corner)
         if self.kind == "linear":
             m, src, absb, coeff = pr.linear_model_vectors(c, rho, self.tags)
@@ -89,6 +89,8 @@ class Case:
             V["absb"][self.regions["facex+"]] *= 1 + eps
         elif change == "coef_last":
             V["coeff"] = np.where(self.last_layer, V["coeff"] * (1 + eps), V["coeff"]).astype(pr.dtype)
+        elif isinstance(change, tuple) and change[0] == "mass":
+            V["m"] = np.where(change[1], V["m"] * (1 + eps), V["m"]).astype(pr.dtype)
         else:
             assert change is None
         return V
@@ -148,9 +150,14 @@ class Case:
             V = fa.FunctionSpace(mesh, self.P)
             per_layer = self.pr.mesh.num_cells // self.n[0]
             mats = tuple(a[mesh.cx0 * per_layer:mesh.cx1 * per_layer] for a in mats)
+        return self.model_on(ctx, mesh, V, tag_box_boundary(mesh), mats, order)
+
+    def model_on(self, ctx, mesh, V, tags, mats, order=None):
+        """The library's model of this case's family on ``mesh`` (a part of the case's mesh, or all of it) with the
+        per-cell materials ``mats`` = (c0, rho0, delta0, beta0) of its cells."""
+        dt_ = self.dtype
         c, rho, delta, beta = (np.array(a, dtype=dt_) for a in mats)
         o = self.order if order is None else order
-        tags = tag_box_boundary(mesh)
         if self.kind == "linear":
             return fa.LinearSpectralExplicit(mesh, tags, self.P, c, rho, F0, self.p0, S0, o, self.dt, V=V, ctx=ctx)
         if self.kind == "lossy":
@@ -238,10 +245,29 @@ FP32_LONG = {"linear-p6-long": dict(kind="linear", n=(4, 3, 2), P=6, nsteps=50, 
 # two x-slabs (test_gpu_config5_fp32.py's partition in small)
 FP32_SLABS = {f"{_kind}-slabs-p{_P}": dict(kind=_kind, n=_n, P=_P, L=0.024, nsteps=15, dtype=np.float32)
               for _kind in ("lossy", "westervelt") for _P, _n in ((6, (6, 3, 3)), (4, (8, 4, 4)))}
+# two x-slabs at RK order 3 (stage kinds 0, 1, 1 in fp32 across the interface).  20 steps at cfl = 0.1, the run of
+# the *-rk{1,2,3} cases: the float oracle alone keeps the yardstick far below the guards' cap of 128 ulp at that
+# length (largest measures 8.4 ulp of 2^-23 in v, on the face x = 0, and 5.7 ulp in u, the vector's max error), so the
+# run was not shortened.
+FP32_SLABS_RK3 = {"lossy-slabs-p4-rk3": dict(kind="lossy", n=(8, 4, 4), P=4, L=0.024, order=3, cfl=0.1, nsteps=20,
+                                             dtype=np.float32)}
 # enough blocks (320 of two elements) for walking workgroups to walk: more blocks than the device has CUs
 FP32_WALK = {f"{_kind}-walk-p{_P}": dict(kind=_kind, n=(10, 8, 8), P=_P, L=0.02, dtype=np.float32)
              for _kind in ("linear", "westervelt") for _P in (4, 6)}
-FP32_CASES = {**FP32_RUNS, **FP32_LONG, **FP32_SLABS, **FP32_WALK}
+FP32_CASES = {**FP32_RUNS, **FP32_LONG, **FP32_SLABS, **FP32_SLABS_RK3, **FP32_WALK}
+
+# ---- the multi-rank matrix (test_gpu_multirank_matrix.py): every stage kind and family across rank interfaces --------
+# name -> (constructor keywords).  "hex" and "quad": the smallest boxes that still cut into 2 and 3 x-slabs with ragged
+# blocks (3211 and 1073 DOFs); "quadrants": the box of test_multirank's 2 x 2 partition in x-y, one line of DOFs held
+# by four ranks (quadrant_partition.py).  rk4 cases serve both the lean form and lean_rk4 = 0: the oracle is the same.
+MR_SHAPES = {"hex": dict(n=(6, 4, 4), P=3), "quad": dict(n=(9, 7), P=4), "quadrants": dict(n=(4, 4, 3), P=3, L=0.016)}
+MR_CASES = {}
+for _shape, _kinds, _orders in (("hex", KINDS, (1, 2, 3, 4)), ("quad", ("lossy", "westervelt"), (2, 4)),
+                                ("quadrants", KINDS, (2, 4))):
+    for _kind in _kinds:
+        for _o in _orders:
+            _kw = dict(nsteps=10) if _o == 4 else dict(order=_o, cfl=0.1, nsteps=20)
+            MR_CASES[f"{_kind}-{_shape}-rk{_o}"] = dict(kind=_kind, **MR_SHAPES[_shape], **_kw)
 
 _cache = {}
 
@@ -250,6 +276,44 @@ def case(orc, name) -> Case:
     if name not in _cache:
         _cache[name] = Case(orc, **CASES[name])
     return _cache[name]
+
+
+def mr_partitions(cs, name):
+    """The partitions a multi-rank case is run on: [(label, {interface: global DOF ids that two ranks share}, sides)],
+    ``sides`` the DOF masks whose mass the guards change -- for x-slabs the element layers left and right of each cut
+    without the cut plane, for the quadrants the DOFs that one rank holds alone."""
+    out = []
+    if "-quadrants-" in name:
+        from quadrant_partition import quadrant_parts, shared_sets
+        parts = quadrant_parts(cs.pr, cs.tags)
+        count = np.zeros(cs.pr.ndofs, int)
+        for p in parts:
+            count[p.gids] += 1
+        sides = []
+        for p in parts:
+            mask = np.zeros(cs.pr.ndofs, bool)
+            mask[p.gids] = True
+            sides.append(mask & (count == 1))
+        return [("quadrants", shared_sets(parts), sides)]
+    layer = np.zeros(cs.pr.ndofs, int)
+    for i in range(cs.n[0]):                             # (a DOF on two layers counts to the right one)
+        layer[cs.regions[f"layer{i}"]] = i
+    for size in (2, 3):
+        planes = slab_interface_regions(cs.pr, size)
+        sides = []
+        for r in range(1, size):
+            cut = (cs.n[0] * r) // size                   # element layers [0, cut) left of the cut (BoxMesh.cx0)
+            plane = np.zeros(cs.pr.ndofs, bool)
+            plane[planes[f"cut{r - 1}|{r}"]] = True
+            sides += [(layer < cut) & ~plane, (layer >= cut) & ~plane]
+        out.append((f"{size} slabs", planes, sides))
+    return out
+
+
+def mr_case(orc, name) -> Case:
+    if ("mr", name) not in _cache:
+        _cache["mr", name] = Case(orc, **MR_CASES[name])
+    return _cache["mr", name]
 
 
 def fp32_case(orc, name) -> Case:

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import fp32_budget as fb
-from live_cases import FP32_LONG, FP32_RUNS, FP32_SLABS, FP32_WALK, case, fp32_case
+from live_cases import FP32_LONG, FP32_RUNS, FP32_SLABS, FP32_SLABS_RK3, FP32_WALK, case, fp32_case
 from util import assert_live, slab_interface_regions
 
 
@@ -54,10 +54,12 @@ def test_fixed_step_count_in_float_composes(orc, name):
 
 
 def _regions(cs, name):
-    return {**cs.regions, **slab_interface_regions(cs.pr, 2)} if name in FP32_SLABS else cs.regions
+    slabs = name in FP32_SLABS or name in FP32_SLABS_RK3
+    return {**cs.regions, **slab_interface_regions(cs.pr, 2)} if slabs else cs.regions
 
 
-@pytest.mark.parametrize("name", list(FP32_RUNS) + list(FP32_LONG) + list(FP32_SLABS) + list(FP32_WALK))
+@pytest.mark.parametrize("name", list(FP32_RUNS) + list(FP32_LONG) + list(FP32_SLABS) + list(FP32_SLABS_RK3)
+                         + list(FP32_WALK))
 def test_case_is_live_and_its_yardstick_sane(orc, name):
     cs = fp32_case(orc, name)
     (u0, v0), r32, r64 = cs.fp32_refs()
@@ -71,7 +73,7 @@ def test_case_is_live_and_its_yardstick_sane(orc, name):
         assert not big, f"{name}/{f}: yardstick above 128 ulp in {big}"
 
 
-@pytest.mark.parametrize("name", list(FP32_RUNS) + list(FP32_LONG) + list(FP32_WALK))
+@pytest.mark.parametrize("name", list(FP32_RUNS) + list(FP32_LONG) + list(FP32_SLABS_RK3) + list(FP32_WALK))
 @pytest.mark.parametrize("change", ["absb_far", "coef_last"])
 def test_budget_at_its_ceiling_sees_a_1e4_mistake(orc, name, change):
     cs = fp32_case(orc, name)

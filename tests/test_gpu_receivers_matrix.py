@@ -255,6 +255,45 @@ def test_recording_without_any_receiver(orc):
     assert np.isfinite(u_after).all() and np.abs(u_after).max() > 0
 
 
+def test_a_smaller_capacity_after_a_larger_one_is_the_limit(orc):
+    """record(1, 8), eight steps, then record(1, 4) and eight more: the second recording takes four records, those of
+    its first four steps, bit-equal to a model that recorded with capacity 4 from the start; and
+    fus_model_get_records, called as a C caller does with ``out`` sized for what it asked for, writes 4 npts values."""
+    from fenicsxfus_amd import _abi
+
+    cs, opts, which, p = rec_case(orc, "linear-rk4")
+    dt = cs.dt
+    t = [0.0] + times_after(0.0, dt, 16)
+    ctx, mdl, _ = rec_model(cs, opts)
+    ctx2, twin, _ = rec_model(cs, opts)
+    try:
+        mdl.set_receivers(p.pts), twin.set_receivers(p.pts)
+        n = p.n_inside
+        mdl.record(every=1, capacity=8, which=which)
+        mdl.rk4_steps(0.0, dt, 8)
+        assert mdl.records()[1].shape == (8, n)
+        mdl.record(every=1, capacity=4, which=which)
+        mdl.rk4_steps(t[8], dt, 8)
+        out = np.full(8 * n, np.nan)                       # twice what the caller asked for, to see an overrun
+        times = np.full(8, np.nan)
+        nrec = C.c_int64(-1)
+        _abi.check(_abi.lib().fus_model_get_records(mdl.h, out.ctypes.data_as(C.c_void_p),
+                                                    times.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nrec)))
+        twin.rk4_steps(0.0, dt, 8)
+        twin.record(every=1, capacity=4, which=which)
+        twin.rk4_steps(t[8], dt, 8)
+        ttimes, trec = twin.records()
+    finally:
+        mdl.close(), ctx.close(), twin.close(), ctx2.close()
+    assert n > 0 and cs.dtype == np.float64
+    assert nrec.value == 4
+    assert np.isfinite(out[:4 * n]).all() and np.isnan(out[4 * n:]).all() and np.isnan(times[4:]).all()
+    assert np.allclose(times[:4], t[9:13], rtol=1e-12, atol=0.0)
+    assert trec.shape == (4, n) and np.array_equal(ttimes, times[:4])
+    assert np.array_equal(out[:4 * n].reshape(4, n), trec)
+    assert not np.array_equal(trec[0], trec[3])
+
+
 # ---- (4) several ranks ---------------------------------------------------------------------------------------------------
 MR_CASES = {            # transport, slabs, degree, dimension, monitor beside the recording
     "group-2": ("local", 2, 4, 3, True),

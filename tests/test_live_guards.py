@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import test_multirank as mr
-from live_cases import CASES, TOL_RK, case
+from live_cases import CASES, MR_CASES, TOL_RK, case, mr_case, mr_partitions
 from util import assert_live, layer_and_face_regions, slab_interface_regions
 
 
@@ -55,3 +55,42 @@ def test_slab_problem_is_live_bounded_and_sensitive(orc, size):
             mask = side & ~plane
             _, _, du, dv = mr.single_rank_reference(orc, "live", mass_scale=(mask, 1 + 1e-6))
             assert max(relmax(du, u), relmax(dv, v)) > 100 * TOL_RK
+
+
+def _plane_diff(a, b, idx):
+    """The difference of the states a and b on the DOFs idx, relative to b's max: the smaller of u's and v's."""
+    return min(np.abs(x[idx] - y[idx]).max() / np.abs(y).max() for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", list(MR_CASES))
+def test_multirank_case_is_live_bounded_and_sensitive(orc, name):
+    """The cases of test_gpu_multirank_matrix.py, against the reference that file uses (the oracle's fixed step
+    count): live in every layer, on every face and on every interface of every partition the case is run on; bounded;
+    sensitive to the far face's absorbing weight, the last layer's coefficient and the mass on either side of each
+    cut; and, for the orders 1-3, apart from the neighbouring orders' states on every interface -- a stage update
+    of another order's table on the interface DOFs alone is then far above the tolerance."""
+    cs = mr_case(orc, name)
+    u0, v0 = cs.start()
+    half = cs.oracle(u0, v0, nsteps=cs.nsteps // 2, fixed=True)
+    u, v = cs.oracle(u0, v0, fixed=True)
+    partitions = mr_partitions(cs, name)
+    for label, planes, _ in partitions:
+        assert all(len(idx) > 0 for idx in planes.values()), label
+        assert_live((u, v), {**cs.regions, **planes})
+    for a, b in ((half[0], u0), (u, u0), (half[1], v0), (v, v0)):
+        assert np.abs(a).max() < 10 * np.abs(b).max()
+    for change in ("absb_far", "coef_last"):
+        du = cs.oracle(u0, v0, change=change, eps=1e-6, fixed=True)
+        assert max(relmax(du[0], u), relmax(du[1], v)) > 100 * TOL_RK, change
+    for label, _, sides in partitions:
+        for k, mask in enumerate(sides):
+            assert mask.any()
+            du = cs.oracle(u0, v0, change=("mass", mask), eps=1e-6, fixed=True)
+            assert max(relmax(du[0], u), relmax(du[1], v)) > 100 * TOL_RK, (label, k)
+    if cs.order < 4:
+        for other in (cs.order - 1, cs.order + 1):
+            if 1 <= other <= 3:
+                w = cs.oracle(u0, v0, order=other, fixed=True)
+                for label, planes, _ in partitions:
+                    for plane, idx in planes.items():
+                        assert _plane_diff(w, (u, v), idx) > 100 * TOL_RK, (other, label, plane)
