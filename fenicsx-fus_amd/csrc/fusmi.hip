@@ -256,23 +256,11 @@ static int op_setup_device(fus_op* op)
   Layout& L = op->L;
   auto& pool = op->allocs;
 
-  std::vector<ShapeDev> shapes(L.shapes.size());
-  for (size_t i = 0; i < shapes.size(); ++i)
-  {
-    shapes[i].nelem = L.shapes[i].nelem, shapes[i].nloc = L.shapes[i].nloc;
-    shapes[i].nint = L.shapes[i].nint, shapes[i].nrounds = L.shapes[i].nrounds;
-    shapes[i].rounds_off = L.shapes[i].rounds_off, shapes[i].ldm_off = L.shapes[i].ldm_off;
-  }
-  int32_t *d_blk_shape, *d_elem_off, *d_int_off, *d_sh_gidx;
-  int64_t* d_sh_off;
-  ShapeDev* d_shapes;
+  int32_t* d_sh_gidx;
+  BlockRecord* d_blk_rec;
   int16_t* d_rounds;
   uint16_t* d_ldm;
-  FUSCHK(upload(pool, &d_blk_shape, L.blk_shape, st));
-  FUSCHK(upload(pool, &d_shapes, shapes, st));
-  FUSCHK(upload(pool, &d_elem_off, L.blk_elem_off, st));
-  FUSCHK(upload(pool, &d_int_off, L.blk_int_off, st));
-  FUSCHK(upload(pool, &d_sh_off, L.blk_sh_off, st));
+  FUSCHK(upload(pool, &d_blk_rec, L.blk_rec, st));
   FUSCHK(upload(pool, &d_sh_gidx, L.sh_gidx, st));
   FUSCHK(upload(pool, &d_rounds, L.rounds, st));
   L.ldm.resize((L.ldm.size() + 15) & ~(size_t)15);  // 16-byte tail for the vector copy
@@ -290,8 +278,7 @@ static int op_setup_device(fus_op* op)
   int32_t* d_sh_ppos;
   FUSCHK(upload(pool, &d_sh_ppos, L.pair_pos, st));
   op->A.sh_ppos = d_sh_ppos;
-  op->A.blk_shape = d_blk_shape, op->A.shapes = d_shapes, op->A.blk_elem_off = d_elem_off;
-  op->A.blk_int_off = d_int_off, op->A.blk_sh_off = d_sh_off, op->A.sh_gidx = d_sh_gidx;
+  op->A.blk_rec = d_blk_rec, op->A.sh_gidx = d_sh_gidx;
   op->A.rounds = d_rounds, op->A.ldm = d_ldm, op->A.nblocks = L.nblocks;
   op->A.lds_nloc = (L.max_nloc + 1) & ~1;
   op->A.waves = L.waves;
@@ -995,7 +982,8 @@ static int stage_end(fus_model* m, int i, double t, double dt)
   if (nloc > 0 && c->planes && (int)op->L.plane_cnt.size() <= (c->planes == 1 ? FUS_MAX_PLANES : c->planes))
   {
     ProfScope ps(c, "stage");
-    const dim3 grid(nblk(nloc)), blk(256);
+    constexpr int W = 16 / (int)sizeof(T);   // dofs per thread: 16-byte accesses
+    const dim3 grid(nblk((nloc + W - 1) / W)), blk(256);
     PartialPlanes PL{};
     PL.bnd0 = (int32_t)op->L.n_partial;
     for (size_t j = 0; j < op->L.plane_cnt.size(); ++j)

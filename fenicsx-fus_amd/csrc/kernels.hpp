@@ -21,24 +21,15 @@
 
 #include "block_variant.hpp"
 #include "geom.hpp"
+#include "layout.hpp"
 #include "source_wave.hpp"
 
 namespace fus
 {
 
-struct ShapeDev
-{
-  int32_t nelem, nloc, nint, nrounds;
-  int64_t rounds_off, ldm_off;
-};
-
 struct BlockArgs
 {
-  const int32_t* blk_shape;
-  const ShapeDev* shapes;
-  const int32_t* blk_elem_off;
-  const int32_t* blk_int_off;
-  const int64_t* blk_sh_off;
+  const BlockRecord* blk_rec;  // one 64-byte record per block (layout.hpp): offsets and shape fields
   const int32_t* sh_gidx;
   const int32_t* sh_ppos;  // where each (block, shared slot) pair's partial sum goes (Layout::pair_pos)
   const int16_t* rounds;
@@ -2161,6 +2152,137 @@ __device__ __forceinline__ void elem_stiff_bwd(const DTab<T, N>& Dk, const T (&D
 #define FUS_PF1(T, P, OP, ATOMIC, GEOM, TD)                                                         \
   (((P) >= 5 && (P) <= 7 && (OP) == OP_STIFFNESS && (GEOM) == GEOM_STREAM && (TD) == 3) ? 1 : 0)
 
+template <typename T>
+struct LeanRK
+{
+  T b0dt, pdt, third;   // see StageArgs
+};
+
+// The vectors a stage kind reads and writes, as bits in the order of StageRegs' fields: what stage_update_dof loads
+// and stores around stage_kv / stage_finish below, which must touch no other field (a vector missing here reads as
+// zero and fails the oracle comparison of that stage kind, tests/test_gpu_live_state.py and test_gpu_block_records.py).
+enum : int { SR_MINV = 1, SR_M0 = 2, SR_MN1 = 4, SR_U0 = 8, SR_V0 = 16, SR_UN = 32, SR_VN = 64, SR_UA = 128, SR_VA = 256 };
+// (wv: the Westervelt form, which also reads its stage input u_n, v_n -- u0, v0 at the first stage -- and m0, mn1 for minv)
+__host__ __device__ constexpr int stage_reads(int st, bool wv)
+{
+  return ((st == 0 || st == 4) ? SR_U0 | SR_V0
+          : st == 3            ? SR_VN | SR_UA | SR_VA
+          : st == 5            ? SR_VN | SR_V0 | SR_UN
+          : st == 6            ? SR_VN | SR_V0 | SR_UA | SR_UN
+          : st == 7            ? SR_VN | SR_V0 | SR_UA | SR_VA | SR_UN
+                               : SR_VN | SR_UA | SR_VA | SR_U0 | SR_V0)
+         | (wv ? SR_M0 | SR_MN1 | (stage_is_first(st) ? SR_U0 | SR_V0 : SR_UN | SR_VN) : SR_MINV);
+}
+__host__ __device__ constexpr int stage_writes(int st)
+{
+  return (st == 3 || st == 7) ? SR_U0 | SR_V0 : (st >= 4 ? SR_UN | SR_VA : SR_UA | SR_VA | SR_UN | SR_VN);
+}
+
+// One dof's entries of the stage's vectors (ua, va: the entries of u_, v_): read where the stage kind reads them,
+// overwritten where it writes them.
+template <typename T>
+struct StageRegs
+{
+  T minv, m0, mn1, u0, v0, un, vn, ua, va;
+};
+
+// a * b + c rounded once
+__device__ __forceinline__ double fmadd(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float fmadd(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// The arithmetic of the stage update of one dof, on registers: the one place it is written down, for the one-dof
+// form (stage_update_dof) and for the 16-byte form of k_shared_stage_planes alike.  Returns the velocity the NEXT
+// stage starts from: vn' (stages 0-2) or the new v0 (stage 3).
+// Every fused multiply-add is written out and the compiler's own contraction is off: which product of
+// a * b - c * d it fuses, and whether it packs products of neighbouring dofs into two-lane instructions first,
+// depends on the code around the expression (four dofs side by side in fp32 came out differently from one), and the
+// plane form and the CSR form of the shared-dof stage kernel must give the same bits.  The forms are the ones the
+// compiler chose for the one-dof fp64 kernels (the left product of a sum of two products is fused), so fp64 results
+// are what they were.
+// (in two parts, so that the one-dof form can ask for the second part's operands after the first part's division)
+// kv = M^-1 b from the vectors stage_kv_reads names
+__host__ __device__ constexpr int stage_kv_reads(int st, bool wv)
+{
+  return wv ? SR_M0 | SR_MN1 | (stage_is_first(st) ? SR_U0 | SR_V0 : SR_UN | SR_VN) : SR_MINV;
+}
+template <typename T, int STAGE>
+__device__ __forceinline__ T stage_kv(T acc, bool wv, const StageRegs<T>& r)
+{
+#pragma clang fp contract(off)
+  if (wv)  // Westervelt (see StageArgs): stage inputs u_n, v_n are u0, v0 at the first stage
+  {
+    // kv = (acc - mn1 vs^2) / (m0 + mn1 us)
+    const T us = stage_is_first(STAGE) ? r.u0 : r.un, vs = stage_is_first(STAGE) ? r.v0 : r.vn;
+    return fmadd(-vs, r.mn1 * vs, acc) / fmadd(r.mn1, us, r.m0);
+  }
+  return acc * r.minv;
+}
+template <typename T, int STAGE>
+__device__ __forceinline__ T stage_finish(T kv, StageRegs<T>& r, T adt, T bdt, const LeanRK<T> R)
+{
+#pragma clang fp contract(off)
+  T vnext;
+  if (STAGE == 0)
+  {
+    const T u = r.u0, v = r.v0;
+    r.ua = fmadd(v, bdt, u);
+    r.va = fmadd(kv, bdt, v);
+    r.un = fmadd(v, adt, u);
+    vnext = fmadd(kv, adt, v);
+    r.vn = vnext;
+  }
+  else if (STAGE == 4)   // stage 0: the input is u0 itself
+  {
+    const T u = r.u0, v = r.v0;
+    r.un = fmadd(v, adt, u);
+    vnext = fmadd(kv, adt, v);
+    r.va = vnext;   // V_1
+  }
+  else if (STAGE == 3)
+  {
+    r.u0 = fmadd(r.vn, bdt, r.ua);
+    vnext = fmadd(kv, bdt, r.va);
+    r.v0 = vnext;
+  }
+  else if (STAGE == 5)   // stage 1: un = u0 + pdt v0, vn = V_1
+  {
+    const T w = r.vn, v = r.v0, xs = r.un;
+    r.un = xs + fmadd(w, adt, -(v * R.pdt));   // xs + (w adt - v pdt)
+    vnext = fmadd(kv, adt, v);
+    r.va = vnext;   // V_2
+  }
+  else if (STAGE == 6)   // stage 2: un = u0 + pdt V_1, vn = V_2, u_ = V_1
+  {
+    const T w = r.vn, v = r.v0, va = r.ua, xs = r.un;
+    r.un = xs + fmadd(w, adt, -(va * R.pdt));   // xs + (w adt - va pdt)
+    vnext = fmadd(kv, adt, v);
+    r.va = vnext;   // V_3
+  }
+  else if (STAGE == 7)   // stage 3: un = u0 + pdt V_2, vn = V_3, u_ = V_1, v_ = V_2; the new state
+  {
+    const T w = r.vn, v = r.v0, va = r.ua, vb = r.va, xs = r.un;
+    // u0 = (xs - vb pdt) + (2 (va + vb) + (v + w)) b0dt ;  v0 = kv bdt + ((2 vb + (va + w)) - v) / 3
+    r.u0 = fmadd(fmadd(va + vb, T(2), v + w), R.b0dt, fmadd(-vb, R.pdt, xs));
+    vnext = fmadd(kv, bdt, (fmadd(vb, T(2), va + w) - v) * R.third);
+    r.v0 = vnext;
+  }
+  else
+  {
+    const T w = r.vn, ua = r.ua, va = r.va;
+    r.ua = fmadd(w, bdt, ua);
+    r.va = fmadd(kv, bdt, va);
+    r.un = fmadd(w, adt, r.u0);
+    vnext = fmadd(kv, adt, r.v0);
+    r.vn = vnext;
+  }
+  return vnext;
+}
+template <typename T, int STAGE>
+__device__ __forceinline__ T stage_update_regs(T acc, bool wv, StageRegs<T>& r, T adt, T bdt, const LeanRK<T> R)
+{
+  return stage_finish<T, STAGE>(stage_kv<T, STAGE>(acc, wv, r), r, adt, bdt, R);
+}
+
 // Fused RK4 stage update of ONE dof s whose right-hand side sum `acc` (= b) is complete.
 // kv = b * minv  (Linear.hpp:212-221), ku = vn (f0, :171-174).
 //   STAGE 0 : vn == v0, un == u0, u_ == u0, v_ == v0 (aliases are not read twice)
@@ -2171,87 +2293,85 @@ __device__ __forceinline__ void elem_stiff_bwd(const DTab<T, N>& Dk, const T (&D
 //
 // Model vectors are read / written once per stage: non-temporal, so that the partial slab (written
 // just before by k_block_op) stays cache resident.
-template <typename T>
-struct LeanRK
-{
-  T b0dt, pdt, third;   // see StageArgs
-};
-
-template <typename T, int STAGE>
-__device__ __forceinline__ T stage_update_dof(int64_t s, T acc, const T* __restrict__ minv,
+//
+// The stage update of the dof(s) at index s: V = T, one dof; V = a 16-byte vector of T, the dofs s, s + 1, ... (s a
+// multiple of the vector width), every vector the stage reads or writes moved by one non-temporal 16-byte access and
+// each dof's arithmetic done by stage_update_regs on its own component.  acc / the return value: per dof.  nv < W:
+// only the first nv dofs exist (the end of a range whose length is no multiple of W); they move dof by dof.
+// FUS_STAGE_VECTORS(X): X(field of StageRegs, vector, bit)
+#define FUS_STAGE_VECTORS(X)                                                                        \
+  X(minv, minv, SR_MINV) X(m0, m0, SR_M0) X(mn1, mn1, SR_MN1) X(u0, u0, SR_U0) X(v0, v0, SR_V0)     \
+  X(un, un, SR_UN) X(vn, vn, SR_VN) X(ua, u_, SR_UA) X(va, v_, SR_VA)
+template <typename T, int STAGE, typename V = T>
+__device__ __forceinline__ V stage_update_dof(int64_t s, V acc, const T* __restrict__ minv,
                                                  T* __restrict__ vn, T* __restrict__ un,
                                                  T* __restrict__ u0, T* __restrict__ v0,
                                                  T* __restrict__ u_, T* __restrict__ v_, T adt, T bdt,
                                                  const T* __restrict__ m0, const T* __restrict__ mn1,
-                                                 const LeanRK<T> R)
+                                                 const LeanRK<T> R, int nv = (int)(sizeof(V) / sizeof(T)))
 {
-#define FUS_LD(p) __builtin_nontemporal_load(&(p)[s])
-#define FUS_ST(p, val) __builtin_nontemporal_store((val), &(p)[s])
-  T kv;
-  if (mn1)  // Westervelt (see StageArgs): stage inputs u_n, v_n are u0, v0 at the first stage
+  constexpr int W = (int)(sizeof(V) / sizeof(T));
+  const bool wv = mn1 != nullptr;
+  const bool whole = W == 1 || nv == W;
+  StageRegs<V> q{};   // zeros where the stage reads nothing
+  const int reads = stage_reads(STAGE, wv);
+  // the vectors among `mask` that the stage reads -> q
+  auto load = [&](int mask) __attribute__((always_inline))
   {
-    const T us = stage_is_first(STAGE) ? u0[s] : un[s], vs = stage_is_first(STAGE) ? v0[s] : vn[s];
-    kv = (acc - mn1[s] * vs * vs) / (m0[s] + mn1[s] * us);
+#define FUS_LD(f, p, bit)                                                                           \
+  if (reads & mask & (bit))                                                                         \
+  {                                                                                                 \
+    if (whole)                                                                                      \
+      q.f = __builtin_nontemporal_load(reinterpret_cast<const V*>(&(p)[s]));                        \
+    else if constexpr (W > 1)                                                                       \
+      for (int e = 0; e < W; ++e)                                                                   \
+        if (e < nv)                                                                                 \
+          q.f[e] = __builtin_nontemporal_load(&(p)[s + e]);                                         \
   }
-  else
-    kv = acc * FUS_LD(minv);
-  T vnext;  // the velocity the NEXT stage starts from: vn' (stages 0-2) or the new v0 (stage 3)
-  if (STAGE == 0)
-  {
-    const T u = FUS_LD(u0), v = FUS_LD(v0);
-    FUS_ST(u_, v * bdt + u);
-    FUS_ST(v_, kv * bdt + v);
-    FUS_ST(un, v * adt + u);
-    vnext = kv * adt + v;
-    FUS_ST(vn, vnext);
-  }
-  else if (STAGE == 4)   // stage 0: the input is u0 itself
-  {
-    const T u = FUS_LD(u0), v = FUS_LD(v0);
-    FUS_ST(un, v * adt + u);
-    vnext = kv * adt + v;
-    FUS_ST(v_, vnext);   // V_1
-  }
-  else if (STAGE == 3)
-  {
-    FUS_ST(u0, FUS_LD(vn) * bdt + FUS_LD(u_));
-    vnext = kv * bdt + FUS_LD(v_);
-    FUS_ST(v0, vnext);
-  }
-  else if (STAGE == 5)   // stage 1: un = u0 + pdt v0, vn = V_1
-  {
-    const T w = FUS_LD(vn), v = FUS_LD(v0), xs = FUS_LD(un);
-    FUS_ST(un, xs + (w * adt - v * R.pdt));
-    vnext = kv * adt + v;
-    FUS_ST(v_, vnext);   // V_2
-  }
-  else if (STAGE == 6)   // stage 2: un = u0 + pdt V_1, vn = V_2, u_ = V_1
-  {
-    const T w = FUS_LD(vn), v = FUS_LD(v0), va = FUS_LD(u_), xs = FUS_LD(un);
-    FUS_ST(un, xs + (w * adt - va * R.pdt));
-    vnext = kv * adt + v;
-    FUS_ST(v_, vnext);   // V_3
-  }
-  else if (STAGE == 7)   // stage 3: un = u0 + pdt V_2, vn = V_3, u_ = V_1, v_ = V_2; the new state
-  {
-    const T w = FUS_LD(vn), v = FUS_LD(v0), va = FUS_LD(u_), vb = FUS_LD(v_), xs = FUS_LD(un);
-    FUS_ST(u0, (xs - vb * R.pdt) + ((va + vb) * T(2) + (v + w)) * R.b0dt);
-    vnext = kv * bdt + ((vb * T(2) + (va + w)) - v) * R.third;
-    FUS_ST(v0, vnext);
-  }
-  else
-  {
-    const T w = FUS_LD(vn);
-    FUS_ST(u_, w * bdt + FUS_LD(u_));
-    FUS_ST(v_, kv * bdt + FUS_LD(v_));
-    FUS_ST(un, w * adt + FUS_LD(u0));
-    vnext = kv * adt + FUS_LD(v0);
-    FUS_ST(vn, vnext);
-  }
+    FUS_STAGE_VECTORS(FUS_LD)
 #undef FUS_LD
+  };
+  V vnext;
+  if constexpr (W == 1)
+  {
+    // one dof (also the odd last dof of a block's interior range, inside the block kernel, where registers are
+    // scarce): the operands of the second part are requested after the first part
+    load(stage_kv_reads(STAGE, wv));
+    const T kv = stage_kv<T, STAGE>(acc, wv, q);
+    load(~stage_kv_reads(STAGE, wv));
+    vnext = stage_finish<T, STAGE>(kv, q, adt, bdt, R);
+  }
+  else
+  {
+    load(~0);
+#pragma unroll
+    for (int e = 0; e < W; ++e)
+    {
+      StageRegs<T> r;
+#define FUS_GET(f, p, bit) r.f = q.f[e];
+      FUS_STAGE_VECTORS(FUS_GET)
+#undef FUS_GET
+      vnext[e] = stage_update_regs<T, STAGE>(acc[e], wv, r, adt, bdt, R);
+#define FUS_PUT(f, p, bit) q.f[e] = r.f;
+      FUS_STAGE_VECTORS(FUS_PUT)
+#undef FUS_PUT
+    }
+  }
+#define FUS_ST(f, p, bit)                                                                           \
+  if constexpr ((stage_writes(STAGE) & (bit)) != 0)                                                 \
+  {                                                                                                 \
+    if (whole)                                                                                      \
+      __builtin_nontemporal_store(q.f, reinterpret_cast<V*>(const_cast<T*>(&(p)[s])));              \
+    else if constexpr (W > 1)                                                                       \
+      for (int e = 0; e < W; ++e)                                                                   \
+        if (e < nv)                                                                                 \
+          __builtin_nontemporal_store(q.f[e], const_cast<T*>(&(p)[s + e]));                         \
+  }
+  FUS_STAGE_VECTORS(FUS_ST)
 #undef FUS_ST
   return vnext;
 }
+#undef FUS_STAGE_VECTORS
 
 // The block kernel's only argument (read in the kernel through the kernarg segment pointer, see FUS_KARGS).
 template <typename T, int N>
@@ -2384,19 +2504,23 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   // workgroup per block walks one).  While it writes out block k (the epilogue's loads and stores) the
   // global loads of block k + 1's prologue are already in flight, so the two memory-latency phases of
   // consecutive blocks overlap instead of following each other.
-  struct Meta
+  struct Meta   // the fields of the block's record (layout.hpp BlockRecord)
   {
-    ShapeDev sh;
-    int elem_off, int_off;
+    int32_t elem_off, int_off;
     int64_t sh_off;
+    int32_t nelem, nloc, nint, nrounds;
+    int64_t rounds_off, ldm_off;
   };
+  // One scalar load sequence to the block's own cache line, nothing depends on a second load.  The table
+  // is never written while a kernel runs: read through the constant address space, i.e. by scalar loads in every phase.
   auto meta_of = [&](KP q, int bk) -> Meta
   {
+    const BlockRecord __attribute__((address_space(4)))* r
+        = (const BlockRecord __attribute__((address_space(4)))*)q->A.blk_rec + bk;
     Meta M;
-    M.sh = q->A.shapes[q->A.blk_shape[bk]];
-    M.elem_off = q->A.blk_elem_off[bk];
-    M.int_off = q->A.blk_int_off[bk];
-    M.sh_off = q->A.blk_sh_off[bk];
+    M.elem_off = r->elem_off, M.int_off = r->int_off, M.sh_off = r->sh_off;
+    M.nelem = r->nelem, M.nloc = r->nloc, M.nint = r->nint, M.nrounds = r->nrounds;
+    M.rounds_off = r->rounds_off, M.ldm_off = r->ldm_off;
     return M;
   };
   typedef T V2 __attribute__((ext_vector_type(2)));
@@ -2424,7 +2548,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   auto p_idx = [&](KP q, const Meta& M, bool enable, int (&gi)[US]) __attribute__((always_inline))
   {
     FUS_TID();
-    const int nsh = M.sh.nloc - M.sh.nint;
+    const int nsh = M.nloc - M.nint;
     const int32_t* gix = q->A.sh_gidx + M.sh_off;
 #pragma unroll
     for (int u = 0; u < US; ++u)
@@ -2434,7 +2558,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       __attribute__((always_inline))
   {
     FUS_TID();
-    const ShapeDev& sh = M.sh;
+    const Meta& sh = M;
     const T* __restrict__ x = q->x;
     const T* __restrict__ x2 = (NF == 2) ? q->S.x2 : x;
     const T* __restrict__ coef = q->coef;
@@ -2481,7 +2605,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   {
     FUS_PHASE_LDS(q);
     FUS_TID();
-    const ShapeDev& sh = M.sh;
+    const Meta& sh = M;
     const T* __restrict__ x = q->x;
     const T* __restrict__ x2 = (NF == 2) ? q->S.x2 : x;
     const T* __restrict__ coef = q->coef;
@@ -2652,10 +2776,10 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     FUS_LANE_COORDS(q);
     (void)b, (void)c, (void)sA, (void)sB;
     const int slots = (q->A.waves * 64 / LPE) * EPW * EPS;
-    const int nt0 = ATOMIC ? (Mm.sh.nelem + slots - 1) / slots : Mm.sh.nrounds;
+    const int nt0 = ATOMIC ? (Mm.nelem + slots - 1) / slots : Mm.nrounds;
     int e0 = -1;
     if (active && nt0 > 0)
-      e0 = ATOMIC ? (myslot < Mm.sh.nelem ? myslot : -1) : (int)q->A.rounds[Mm.sh.rounds_off + myslot];
+      e0 = ATOMIC ? (myslot < Mm.nelem ? myslot : -1) : (int)q->A.rounds[Mm.rounds_off + myslot];
     elem_fetch<T, N, OP, GEOM, TD>(inA, e0, q->geo, Mm.elem_off, p);
   };
   PLoad L;
@@ -2674,7 +2798,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   FUS_PHASE_LDS(qc);
   FUS_LANE_COORDS(qc);
   const Meta M = meta_of(qc, blk);
-  const ShapeDev& sh = M.sh;
+  const Meta& sh = M;
   const int elem_off = M.elem_off;
   // element of this lane group in trip r: conflict-free round table (deterministic mode) or simply
   // the next `slots` elements (atomic mode: no ordering constraint between waves)
@@ -2695,7 +2819,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   else
   {
     FUS_TID();
-    for (int i = tid; i < (M.sh.nloc + 1) / 2; i += nthr)
+    for (int i = tid; i < (M.nloc + 1) / 2; i += nthr)
       reinterpret_cast<A2*>(y_l)[i] = A2(0.0);
   }
 #else
@@ -2835,7 +2959,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   FUS_PHASE_LDS(qe);
   FUS_TID();
   const Meta M = meta_of(qe, blk);
-  const ShapeDev& sh = M.sh;
+  const Meta& sh = M;
   const int int_off = M.int_off;
   const int64_t sh_off = M.sh_off;
   StageArgs<T> S;
@@ -2850,6 +2974,14 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
 #pragma unroll
   for (int u = 0; u < US; ++u)
     ppv[u] = (tid + u * nthr < nsh) ? pp[tid + u * nthr] : -1;
+  // the block's range of boundary entries: requested here too (two scalar registers), so that the branch on it
+  // after the barrier does not start with a memory round trip of its own
+  int bnd_k0 = 0, bnd_k1 = 0;
+  if (STAGE != STAGE_NONE)
+  {
+    const int32_t __attribute__((address_space(4)))* bo = (const int32_t __attribute__((address_space(4)))*)S.blk_bnd_off + blk;
+    bnd_k0 = bo[0], bnd_k1 = bo[1];
+  }
 
   // ---- epilogue: each dof written once ----
   const int nvec = sh.nint >> 1;
@@ -3017,7 +3149,12 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   {
     // boundary terms of block-interior dofs (Linear.hpp:205; forms.py:38-39 collocated):
     // b += g(t) src - abs * v_stage ; every entry is a distinct dof
+#ifdef FUS_PROBE_BND_LATE   // developer probe (A/B of the early request): the range is read here, behind the barrier
     const int k0 = S.blk_bnd_off[blk], k1 = S.blk_bnd_off[blk + 1];
+    (void)bnd_k0, (void)bnd_k1;
+#else
+    const int k0 = bnd_k0, k1 = bnd_k1;
+#endif
     if (k1 > k0)
     {
       const T* vstage = stage_is_first(STAGE) ? S.v0 : S.vn;
@@ -3115,12 +3252,13 @@ struct BndNext
 template <typename T>
 __device__ __forceinline__ void boundary_next(const BndNext<T>& B, int32_t last_pair, T vnext)
 {
+#pragma clang fp contract(off)   // written out like stage_update_regs: the same bits from every kernel form
   if (B.enabled && last_pair >= B.npairs)
   {
     const int32_t k = last_pair - B.npairs;
-    T v = B.gnext * B.srcw[k] - B.absw[k] * vnext;
+    T v = fmadd(B.gnext, B.srcw[k], -(B.absw[k] * vnext));
     if (B.src2w)
-      v += B.dgnext * B.src2w[k];
+      v = fmadd(B.dgnext, B.src2w[k], v);
     B.partial[last_pair] = v;
   }
 }
@@ -3141,6 +3279,9 @@ struct PartialPlanes
 // order, the order of the CSR form below: same bits), then the boundary term of a shared boundary dof
 // (bnd_mask: one bit per dof, bnd_base: boundary dofs ahead of the 64-dof word; the k-th boundary dof's term is
 // in slot PL.bnd0 + k), fused with the RK4 stage update.  No index list is read: every access is at s.
+// A thread takes 16 bytes of consecutive dofs (two in fp64, four in fp32): planes, minv and the stage's vectors move
+// in 16-byte accesses, non-temporal where this kernel is their last reader; the sum of each dof is formed exactly as
+// above (the vectors passed in start on a 16-byte boundary: the shared range does, Layout::n_int_pad).
 template <typename T, int STAGE>
 __global__ void __launch_bounds__(256)
 k_shared_stage_planes(int64_t n, const PartialPlanes PL, const uint64_t* __restrict__ bnd_mask,
@@ -3149,29 +3290,67 @@ k_shared_stage_planes(int64_t n, const PartialPlanes PL, const uint64_t* __restr
                       T* __restrict__ v0, T* __restrict__ u_, T* __restrict__ v_, T adt, T bdt,
                       const T* __restrict__ m0, const T* __restrict__ mn1, const BndNext<T> B, const LeanRK<T> R)
 {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  constexpr int W = 16 / (int)sizeof(T);
+  typedef T V __attribute__((ext_vector_type(W)));
+  const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * W;
   if (s >= n)
     return;
-  T acc = T(0);
+  T acc[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    acc[e] = T(0);
 #pragma unroll
   for (int j = 0; j < FUS_MAX_PLANES; ++j)
   {
-    if (s < PL.cnt[j])
-      acc += partial[(int64_t)PL.off[j] + s];
-  }
-  int32_t pair = -1;
-  if (bnd_mask)
-  {
-    const uint64_t w = bnd_mask[s >> 6];
-    const int bit = (int)(s & 63);
-    if ((w >> bit) & 1ull)
+    const int64_t cnt = PL.cnt[j], off = PL.off[j];
+    if (s + W <= cnt)   // (plane_off is a multiple of 16 dofs: verify_layout)
     {
-      pair = PL.bnd0 + bnd_base[s >> 6] + __builtin_popcountll(w & ((1ull << bit) - 1ull));
-      acc += partial[pair];
+      const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(partial + off + s));
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        acc[e] += v[e];
+    }
+    else
+    {
+      // the plane ends inside this vector: dof by dof
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        if (s + e < cnt)
+          acc[e] += partial[off + s + e];
     }
   }
-  const T vnext = stage_update_dof<T, STAGE>(s, acc, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0, mn1, R);
-  boundary_next<T>(B, pair, vnext);
+  int32_t pair[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    pair[e] = -1;
+  if (bnd_mask)
+  {
+    // s is a multiple of W, W divides 64: the W dofs share one mask word
+    const uint64_t w = bnd_mask[s >> 6];
+    const int bit0 = (int)(s & 63);
+    if ((w >> bit0) & ((1ull << W) - 1ull))
+    {
+      const int32_t base = PL.bnd0 + bnd_base[s >> 6];
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        if ((w >> (bit0 + e)) & 1ull)
+        {
+          pair[e] = base + __builtin_popcountll(w & ((1ull << (bit0 + e)) - 1ull));
+          acc[e] += partial[pair[e]];
+        }
+    }
+  }
+  V av;
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    av[e] = acc[e];
+  // (the last thread of a range whose length is no multiple of W updates fewer dofs)
+  const int nv = (n - s < W) ? (int)(n - s) : W;
+  const V vnext = stage_update_dof<T, STAGE, V>(s, av, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0, mn1, R, nv);
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    if (e < nv)
+      boundary_next<T>(B, pair[e], vnext[e]);
 }
 
 // Shared dofs of one rank, CSR form (more than FUS_MAX_PLANES sharers of one dof, or option "planes" = 0):

@@ -407,7 +407,22 @@ std::string build_layout(Layout& L, int P, int64_t ncells, int64_t ndofs,
   L.n_partial = cursor + (L.npairs - if_first);
   if (L.n_partial + L.n_shared > 2000000000ll)
     return "partial slab exceeds int32 indexing";
+  L.blk_rec = block_records(L);
   return "";
+}
+
+std::vector<BlockRecord> block_records(const Layout& L)
+{
+  std::vector<BlockRecord> rec(L.nblocks);
+  for (int32_t b = 0; b < L.nblocks; ++b)
+  {
+    const Layout::Shape& sh = L.shapes[L.blk_shape[b]];
+    BlockRecord& r = rec[b];   // (value-initialised: the padding is zero)
+    r.elem_off = L.blk_elem_off[b], r.int_off = L.blk_int_off[b], r.sh_off = L.blk_sh_off[b];
+    r.nelem = sh.nelem, r.nloc = sh.nloc, r.nint = sh.nint, r.nrounds = sh.nrounds;
+    r.rounds_off = sh.rounds_off, r.ldm_off = sh.ldm_off;
+  }
+  return rec;
 }
 
 std::string verify_layout(const Layout& L, const int32_t* dm)
@@ -492,6 +507,12 @@ std::string verify_layout(const Layout& L, const int32_t* dm)
         return "two pairs share a partial position";
     }
   }
+  // every plane starts on a multiple of 16 values: k_shared_stage_planes reads it in 16-byte vectors
+  for (int64_t off : L.plane_off)
+    if (off % 16)
+      return "plane not aligned";
+  if ((int64_t)L.blk_rec.size() != L.nblocks)
+    return "block records missing";
   for (int64_t s = 0; s < L.n_shared; ++s)
     for (int64_t k = L.sh_ptr[s]; k < L.sh_ptr[s + 1]; ++k)
     {

@@ -16,6 +16,19 @@
 namespace fus
 {
 
+// Everything the block kernel needs to know about one block before it can issue the block's first vector load: the
+// block's offsets and the fields of its shape, in one 64-byte line (one scalar load sequence, no dependent second load
+// through blk_shape -> shapes).  Built from the Layout vectors below, which stay the host-side record.
+struct alignas(64) BlockRecord
+{
+  int32_t elem_off, int_off;          // Layout::blk_elem_off[b], blk_int_off[b]
+  int64_t sh_off;                     // Layout::blk_sh_off[b]
+  int32_t nelem, nloc, nint, nrounds; // Layout::shapes[blk_shape[b]]
+  int64_t rounds_off, ldm_off;
+  uint8_t pad[16] = {};               // to one line; zero, so that the uploaded table is the same bytes every time
+};
+static_assert(sizeof(BlockRecord) == 64 && alignof(BlockRecord) == 64, "one cache line per block");
+
 struct Layout
 {
   int P = 0, N = 0, Nd = 0;  // Nd = N^tdim nodes per element
@@ -40,6 +53,7 @@ struct Layout
   };
   std::vector<Shape> shapes;
   std::vector<int32_t> blk_shape;     // [nblocks]
+  std::vector<BlockRecord> blk_rec;   // [nblocks] what the device reads per block (block_records)
   std::vector<int16_t> rounds;        // block-relative element index per (round, slot), -1 = idle
   std::vector<uint16_t> ldm;          // local dofmaps
 
@@ -86,6 +100,9 @@ struct Layout
 std::string build_layout(Layout& L, int P, int64_t ncells, int64_t ndofs,
                          const int32_t* tensor_dofmap, const double* centroids, int block_elems,
                          int waves, const uint8_t* force_shared = nullptr, int tdim = 3, int slot_factor = 1);
+
+// One BlockRecord per block from the layout's per-block vectors and shapes (build_layout ends with it).
+std::vector<BlockRecord> block_records(const Layout& L);
 
 // Internal consistency check used by fus_layout_check and the CPU tests.
 std::string verify_layout(const Layout& L, const int32_t* tensor_dofmap);
