@@ -1,6 +1,7 @@
-// core.hpp -- what the units compiled once share beyond host.hpp: fusmi.hip (the operator, the wave models and their
-// C ABI) and thermal.hip (the bioheat model and its C ABI).  degree_unit.hip does not include it.  Everything thermal.hip
-// takes from fusmi.hip is declared here, and nothing else of fusmi.hip has external linkage: this header is the list.
+// core.hpp -- what the units compiled once share beyond host.hpp: fusmi.hip (the operator and its C ABI), wave.hip (the
+// wave models and their C ABI) and thermal.hip (the bioheat model and its C ABI).  degree_unit.hip does not include it.
+// Everything wave.hip and thermal.hip take from fusmi.hip is declared here, and nothing else of fusmi.hip has external
+// linkage: this header is the list.  (The bioheat unit takes nothing from wave.hip but the fus_model fields named below.)
 #ifndef FUS_CORE_HPP
 #define FUS_CORE_HPP
 
@@ -44,7 +45,7 @@ struct fus_model
   int forms = 0;     // fus_ctx::forms at creation
   int lean_rk4 = 1;  // fus_ctx::lean_rk4 at creation
   // The boundary term of the shared boundary dofs rides in pseudo partial slots.  With RK4 the
-  // shared-dof stage kernels write the NEXT stage's values there (boundary_next, kernels.hpp);
+  // shared-dof stage kernels write the NEXT stage's values there (boundary_next, wave_kernels.hpp);
   // bnd_valid / bnd_tn say for which stage time the slots are current, and stage_begin launches
   // k_boundary_partial only when they are not (first stage after init / set, other RK orders).
   bool bnd_valid = false;
@@ -143,7 +144,10 @@ struct ProfScope
   }
 };
 
-// ---- fusmi.hip's typed functions as the bioheat unit calls them, by the operator's scalar type (defined in fusmi.hip) ----
+// ---- fusmi.hip's typed functions as the wave and bioheat units call them, by the operator's scalar type (defined in fusmi.hip) ----
+// The degree unit (degree_unit.hip, DegreeImpl in host.hpp) of a scalar type and degree: the wave models' stage_begin
+// launches the block kernel with its fused stage epilogue through it
+FUS_HIDDEN const DegreeImpl* degree_impl(int dtype, int P);
 // b_internal = A x_internal on device vectors in internal numbering, coef in internal cell order; kind = OP_STIFFNESS | OP_MASS
 FUS_HIDDEN int d_apply_internal(fus_op* op, int kind, const void* coef, const void* x, void* b);
 // the shared-DOF exchange of a vector in its three phases, and all three back to back over RCCL (d_halo_sum)

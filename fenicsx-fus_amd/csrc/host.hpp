@@ -1,7 +1,7 @@
 // host.hpp -- what all translation units of libfusmi share on the host: the units compiled once (fusmi.hip: the
-// operator, the wave models, their C ABI and orchestration; the bioheat model's unit, which adds core.hpp) and
+// operator and its C ABI; wave.hip: the wave models; thermal.hip: the bioheat model -- the three add core.hpp) and
 // degree_unit.hip (compiled once per polynomial degree and scalar type, so that the k_block_op instantiations of the
-// degrees compile in parallel: build.py).  The seam between fusmi.hip and the degree units is DegreeImpl below.
+// degrees compile in parallel: build.py).  The seam between those units and the degree units is DegreeImpl below.
 #ifndef FUS_HOST_HPP
 #define FUS_HOST_HPP
 
@@ -99,7 +99,7 @@ struct fus_ctx
   int mfma = -1;
   int pack32 = -1;  // fp32, degrees 5-7, per-cell geometry: two elements per wave in packed float2 (-1 auto, 0, 1)
   // shared-dof stage kernel reads the partial sums as planes at the dof's own index (1, default) or through the
-  // shared-dof CSR (0; also taken when a dof has more than FUS_MAX_PLANES sharing blocks): same sums, same order
+  // shared-dof CSR (0; also taken when a dof has more than FUS_MAX_PLANES = 16 sharing blocks, wave_kernels.hpp): same sums, same order
   int planes = 1;
   // affine meshes whose cells have mutually orthogonal edges (boxes): the stiffness action in its diagonal-metric
   // form (three 1-D stiffness contractions, kernels.hpp elem_compute) -- 1 (default) where the mesh allows, 0 never
@@ -180,7 +180,7 @@ static int with_kind(int kind, F&& f, std::integer_sequence<int, Ks...>)
   return with_kind<Ks...>(kind, f);
 }
 
-// every kind stage_kind (fusmi.hip) returns: the instantiations of the stage kernels
+// every kind stage_kind (wave.hip) returns: the instantiations of the stage kernels
 #define FUS_STAGE_KINDS                                                                            \
   fus::STAGE_FIRST, fus::STAGE_MID, fus::STAGE_LAST, fus::STAGE_LEAN0, fus::STAGE_LEAN1, fus::STAGE_LEAN2, fus::STAGE_LEAN3
 

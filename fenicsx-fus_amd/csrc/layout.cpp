@@ -87,7 +87,7 @@ std::string build_layout(Layout& L, int P, int64_t ncells, int64_t ndofs,
     std::sort(order.begin() + lf.first, order.begin() + lf.second);
 
   // blocks touching a dof other ranks hold as well go first: the operator launches them ahead of
-  // the rest so that the interface exchange overlaps the remaining blocks (fusmi.hip stage_begin)
+  // the rest so that the interface exchange overlaps the remaining blocks (wave.hip stage_begin)
   L.nblocks_if = 0;
   if (force_shared)
   {

@@ -1,6 +1,6 @@
 // Source waveform of one boundary entry with its own amplitude, delay and (optional) burst duration
 // (fus_model_set_source, fusmi.h).  Plain C++: no HIP header is needed, a host program may include this file; under
-// hipcc the functions are __host__ __device__ and k_source_entries (kernels.hpp) calls them per entry.
+// hipcc the functions are __host__ __device__ and k_source_entries (wave_kernels.hpp) calls them per entry.
 //
 // For the local time s = t - tau, source frequency f, w0 = 2 pi f, ramp length Lr = 4 / f (the reference's
 // window_length, Linear.hpp:185-192) and duration D (0 = continuous wave):
@@ -10,7 +10,7 @@
 //         = 1                                  otherwise
 //   g(s)  = a C W(s) cos(w0 s)
 //   dg(s) = a C (W'(s) cos(w0 s) - W(s) w0 sin(w0 s))
-// with C = scale p0 w0 / s0 as stage_scalars (fusmi.hip) has it.  A duration 0 < D < 2 Lr (the ramps would overlap) is
+// with C = scale p0 w0 / s0 as stage_scalars (wave.hip) has it.  A duration 0 < D < 2 Lr (the ramps would overlap) is
 // refused by fus_source_duration_ok.  Everything is evaluated in double for both scalar types of the library.
 #ifndef FUS_SOURCE_WAVE_HPP
 #define FUS_SOURCE_WAVE_HPP

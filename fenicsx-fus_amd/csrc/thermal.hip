@@ -1,6 +1,6 @@
 // thermal.hip -- the Pennes bioheat model and CEM43 dose (fusmi.h "bioheat"): the fus_thermal handle, its typed
 // implementation and its C entry points, fus_thermal_* and fus_group_thermal_*.  The kernels are in thermal_kernels.hpp;
-// what this unit takes from fusmi.hip is listed in core.hpp.
+// what this unit takes from fusmi.hip (the operator) is listed in core.hpp, with the fields it reads of wave.hip's fus_model.
 #include <memory>
 
 #include "core.hpp"

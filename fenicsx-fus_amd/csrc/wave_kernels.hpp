@@ -1,0 +1,368 @@
+// wave_kernels.hpp -- the device kernels that only the wave models launch (wave.hip alone includes this): the shared-DOF
+// and interface stage kernels, the boundary partials, the field monitor, the receivers and the per-entry source.  The
+// stage algebra they share with the block kernel's epilogue (stage_update_dof and what it uses) is in kernels.hpp.
+#ifndef FUS_WAVE_KERNELS_HPP
+#define FUS_WAVE_KERNELS_HPP
+
+#include "kernels.hpp"
+#include "source_wave.hpp"
+
+namespace fus
+{
+
+// Boundary term of a shared boundary dof for the NEXT stage, produced where that dof's stage update
+// has just finished (its new stage velocity is in a register): the dof's last CSR entry is a pseudo
+// pair (index >= npairs) exactly when it is a boundary dof, and slot k = pair - npairs holds
+//   g(t_next) src[k] - abs[k] v_next (+ dg(t_next) src2[k])        (Linear.hpp:205; forms.py:38-39)
+// -- what k_boundary_partial computes in a launch of its own.  enabled = 0: leave the slots alone.
+template <typename T>
+struct BndNext
+{
+  int enabled;
+  int32_t npairs;
+  const T *srcw, *absw, *src2w;
+  T gnext, dgnext;
+  T* partial;
+};
+
+template <typename T>
+__device__ __forceinline__ void boundary_next(const BndNext<T>& B, int32_t last_pair, T vnext)
+{
+#pragma clang fp contract(off)   // written out like stage_update_regs: the same bits from every kernel form
+  if (B.enabled && last_pair >= B.npairs)
+  {
+    const int32_t k = last_pair - B.npairs;
+    T v = fmadd(B.gnext, B.srcw[k], -(B.absw[k] * vnext));
+    if (B.src2w)
+      v = fmadd(B.dgnext, B.src2w[k], v);
+    B.partial[last_pair] = v;
+  }
+}
+
+
+
+// The partial sums of the rank-local shared dofs as planes (Layout::pair_pos): plane j holds, at the dof's own
+// index, the contribution of the dof's j-th sharing block; cnt[j] dofs (a prefix of the range) have one.
+constexpr int FUS_MAX_PLANES = 16;
+struct PartialPlanes
+{
+  int32_t bnd0;                  // slot of the first boundary term (after every pair's partial sum)
+  int32_t cnt[FUS_MAX_PLANES];   // 0 for the planes that do not exist
+  int32_t off[FUS_MAX_PLANES];
+};
+
+// Shared dofs of one rank, partial sums in planes: sum over the planes in ascending order (= ascending block
+// order, the order of the CSR form below: same bits), then the boundary term of a shared boundary dof
+// (bnd_mask: one bit per dof, bnd_base: boundary dofs ahead of the 64-dof word; the k-th boundary dof's term is
+// in slot PL.bnd0 + k), fused with the RK4 stage update.  No index list is read: every access is at s.
+// A thread takes 16 bytes of consecutive dofs (two in fp64, four in fp32): planes, minv and the stage's vectors move
+// in 16-byte accesses, non-temporal where this kernel is their last reader; the sum of each dof is formed exactly as
+// above (the vectors passed in start on a 16-byte boundary: the shared range does, Layout::n_int_pad).
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256)
+k_shared_stage_planes(int64_t n, const PartialPlanes PL, const uint64_t* __restrict__ bnd_mask,
+                      const int32_t* __restrict__ bnd_base, const T* __restrict__ partial,
+                      const T* __restrict__ minv, T* __restrict__ vn, T* __restrict__ un, T* __restrict__ u0,
+                      T* __restrict__ v0, T* __restrict__ u_, T* __restrict__ v_, T adt, T bdt,
+                      const T* __restrict__ m0, const T* __restrict__ mn1, const BndNext<T> B, const LeanRK<T> R)
+{
+  constexpr int W = 16 / (int)sizeof(T);
+  typedef T V __attribute__((ext_vector_type(W)));
+  const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * W;
+  if (s >= n)
+    return;
+  T acc[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    acc[e] = T(0);
+#pragma unroll
+  for (int j = 0; j < FUS_MAX_PLANES; ++j)
+  {
+    const int64_t cnt = PL.cnt[j], off = PL.off[j];
+    if (s + W <= cnt)   // (plane_off is a multiple of 16 dofs: verify_layout)
+    {
+      const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(partial + off + s));
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        acc[e] += v[e];
+    }
+    else
+    {
+      // the plane ends inside this vector: dof by dof
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        if (s + e < cnt)
+          acc[e] += partial[off + s + e];
+    }
+  }
+  int32_t pair[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    pair[e] = -1;
+  if (bnd_mask)
+  {
+    // s is a multiple of W, W divides 64: the W dofs share one mask word
+    const uint64_t w = bnd_mask[s >> 6];
+    const int bit0 = (int)(s & 63);
+    if ((w >> bit0) & ((1ull << W) - 1ull))
+    {
+      const int32_t base = PL.bnd0 + bnd_base[s >> 6];
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        if ((w >> (bit0 + e)) & 1ull)
+        {
+          pair[e] = base + __builtin_popcountll(w & ((1ull << (bit0 + e)) - 1ull));
+          acc[e] += partial[pair[e]];
+        }
+    }
+  }
+  V av;
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    av[e] = acc[e];
+  // (the last thread of a range whose length is no multiple of W updates fewer dofs)
+  const int nv = (n - s < W) ? (int)(n - s) : W;
+  const V vnext = stage_update_dof<T, STAGE, V>(s, av, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0, mn1, R, nv);
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    if (e < nv)
+      boundary_next<T>(B, pair[e], vnext[e]);
+}
+
+// Shared dofs of one rank, CSR form (more than FUS_MAX_PLANES sharers of one dof, or option "planes" = 0):
+// fixed-order sum of the partials fused with the RK4 stage update of
+// stage_update_dof; vectors are passed offset to the shared range.
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256)
+k_shared_stage(int64_t n, const int32_t* __restrict__ sh_ptr, const int32_t* __restrict__ sh_pairs,
+               const T* __restrict__ partial, const T* __restrict__ minv, T* __restrict__ vn,
+               T* __restrict__ un, T* __restrict__ u0, T* __restrict__ v0, T* __restrict__ u_,
+               T* __restrict__ v_, T adt, T bdt, const T* __restrict__ m0,
+               const T* __restrict__ mn1, const BndNext<T> B, const LeanRK<T> R)
+{
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n)
+    return;
+  T acc = T(0);
+  int32_t pair = 0;
+  for (int32_t k = sh_ptr[s]; k < sh_ptr[s + 1]; ++k)
+  {
+    pair = sh_pairs[k];
+    acc += partial[pair];
+  }
+  const T vnext = stage_update_dof<T, STAGE>(s, acc, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0, mn1, R);
+  boundary_next<T>(B, pair, vnext);
+}
+
+// Interface dofs (held by other ranks too), first half of the exchange: this rank's total of each
+// packed dof = fixed-order sum of its block partials, written to the send buffer and to b.
+// pack_idx[k] is the dof's index in the internal vectors, sh0 the index of shared slot 0; a dof
+// listed for two neighbours is summed twice to the same bits.
+template <typename T>
+__global__ void k_if_reduce_pack(int64_t n, const int32_t* __restrict__ pack_idx, int64_t sh0,
+                                 const int32_t* __restrict__ sh_ptr,
+                                 const int32_t* __restrict__ sh_pairs,
+                                 const T* __restrict__ partial, T* __restrict__ b,
+                                 T* __restrict__ sendbuf)
+{
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n)
+    return;
+  const int64_t u = pack_idx[k], s = u - sh0;
+  T acc = T(0);
+  for (int32_t q = sh_ptr[s]; q < sh_ptr[s + 1]; ++q)
+    acc += partial[sh_pairs[q]];
+  sendbuf[k] = acc;
+  b[u] = acc;
+}
+
+// Second half: every sharer adds the ranks' totals of an interface dof in ascending rank order
+// (identical bits everywhere, see k_unpack_ordered) and finishes the RK stage for it.  Vectors are
+// passed whole (internal numbering); sh0 = internal index of shared slot 0 (for the dof's CSR row).
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256)
+k_if_unpack_stage(int64_t nu, const int32_t* __restrict__ uidx, const int32_t* __restrict__ uptr,
+                  const int32_t* __restrict__ usrc, const T* __restrict__ recvbuf,
+                  const T* __restrict__ b, const T* __restrict__ minv, T* __restrict__ vn,
+                  T* __restrict__ un, T* __restrict__ u0, T* __restrict__ v0, T* __restrict__ u_,
+                  T* __restrict__ v_, T adt, T bdt, const T* __restrict__ m0,
+                  const T* __restrict__ mn1, int64_t sh0, const int32_t* __restrict__ sh_ptr,
+                  const int32_t* __restrict__ sh_pairs, const BndNext<T> B, const LeanRK<T> R)
+{
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nu)
+    return;
+  const int64_t u = uidx[j];
+  const T own = b[u];
+  T acc = T(0);
+  for (int32_t k = uptr[j]; k < uptr[j + 1]; ++k)
+  {
+    const int32_t sidx = usrc[k];
+    acc += (sidx < 0) ? own : recvbuf[sidx];
+  }
+  const T vnext = stage_update_dof<T, STAGE>(u, acc, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0, mn1, R);
+  if (B.enabled)
+    boundary_next<T>(B, sh_pairs[sh_ptr[u - sh0 + 1] - 1], vnext);
+}
+
+// Boundary term of shared boundary dofs, written as one more partial (summed last):
+// slot[k] = g(t) src[k] - abs[k] * v_stage[idx[k]]     (Linear.hpp:205; forms.py:38-39)
+template <typename T>
+__global__ void k_boundary_partial(int64_t nb, const int32_t* __restrict__ idx,
+                                   const T* __restrict__ srcw, const T* __restrict__ absw, T gval,
+                                   const T* __restrict__ src2w, T dgval,
+                                   const T* __restrict__ vstage, T* __restrict__ slot)
+{
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < nb)
+  {
+    T v = gval * srcw[k] - absw[k] * vstage[idx[k]];
+    if (src2w)
+      v += dgval * src2w[k];
+    slot[k] = v;
+  }
+}
+
+// ---- steady-state field monitor (fus_model_monitor, fusmi.h) ---------------------------------------------------
+// One sample = one streaming read-modify-write pass over the per-DOF accumulator planes (structure of arrays, each
+// plane n = n_internal long, n a multiple of 16):
+//   ext  T[2][n]               running max, running min
+//   acc  double[2 + 2 NH][n]   sum, sum of squares, cos_1..cos_NH, sin_1..sin_NH  (always fp64, also for T = float)
+// A thread takes 16 bytes of the state (2 doubles / 4 floats) and updates every plane of those DOFs: one read of the
+// state, one read and one write of each plane, all 16-byte accesses, the planes non-temporal (they are streamed once
+// per sample and are far larger than the last-level cache at production sizes).  The 2 NH phase factors
+// cos / sin(2 pi k f t_j) are computed on the host in double and arrive by value in the kernarg segment; NH is a
+// template parameter so that the plane loop unrolls and nothing is indexed at run time (no scratch).
+// first != 0: the first sample of a window -- max = min = x without reading the (zeroed) extremum planes.
+template <int NH>
+struct MonPhase
+{
+  double c[NH > 0 ? NH : 1], s[NH > 0 ? NH : 1];
+};
+
+template <typename T, int NH>
+__global__ void __launch_bounds__(256)
+k_monitor_accumulate(int64_t nvec, int64_t n, int first, const T* __restrict__ x, T* __restrict__ ext,
+                     double* __restrict__ acc, const MonPhase<NH> ph)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV xv = *reinterpret_cast<const TV*>(x + i * VEC);
+    TV* pmax = reinterpret_cast<TV*>(ext + i * VEC);
+    TV* pmin = reinterpret_cast<TV*>(ext + n + i * VEC);
+    TV mx = xv, mn = xv;
+    if (!first)
+    {
+      const TV omx = __builtin_nontemporal_load(pmax), omn = __builtin_nontemporal_load(pmin);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        mx[j] = xv[j] > omx[j] ? xv[j] : omx[j], mn[j] = xv[j] < omn[j] ? xv[j] : omn[j];
+    }
+    __builtin_nontemporal_store(mx, pmax);
+    __builtin_nontemporal_store(mn, pmin);
+#pragma unroll
+    for (int h = 0; h < VEC / 2; ++h)
+    {
+      const D2 xd = {(double)xv[2 * h], (double)xv[2 * h + 1]};
+      D2* p = reinterpret_cast<D2*>(acc + i * VEC + 2 * h);
+      const int64_t stride = n / 2;   // plane stride in D2
+      __builtin_nontemporal_store(__builtin_nontemporal_load(p) + xd, p);
+      __builtin_nontemporal_store(__builtin_nontemporal_load(p + stride) + xd * xd, p + stride);
+#pragma unroll
+      for (int k = 0; k < NH; ++k)
+      {
+        D2* pc = p + (2 + k) * stride;
+        D2* ps = p + (2 + NH + k) * stride;
+        __builtin_nontemporal_store(__builtin_nontemporal_load(pc) + xd * ph.c[k], pc);
+        __builtin_nontemporal_store(__builtin_nontemporal_load(ps) + xd * ph.s[k], ps);
+      }
+    }
+  }
+}
+
+// Monitor read-out in internal numbering: out = (num * plane) / den, or its square root (RMS), rounded to T.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_monitor_finalise(int64_t n, const double* __restrict__ plane, double num, double den, int root, T* __restrict__ out)
+{
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+  {
+    const double q = (num * plane[i]) / den;
+    out[i] = (T)(root ? sqrt(q) : q);
+  }
+}
+
+// Receiver sampling (the reference evaluates its solution at points with Function::eval after locating their cells:
+// python/src/fenicsxfus/utils.py:10-47, cpp/mwe/parallel_eval_line/main.cpp:49-84).  One wave per receiver r:
+//   out[r] = sum_{i0,i1,i2} l_i0(X0) l_i1(X1) l_i2(X2) vec[idx[r][i0,i1,i2]]
+// on the RESIDENT vector in internal numbering (idx = dof_perm of the receiver's cell dofs, bas = the 1-D Lagrange
+// basis values at the receiver's reference coordinates, both built once in fus_model_set_receivers); lane k adds
+// the entries k, k + 64, ... in that order, then a fixed butterfly: the same bits on every call.
+template <typename T, int TD>
+__global__ void __launch_bounds__(256)
+k_sample(int64_t npts, int N, const int32_t* __restrict__ idx, const T* __restrict__ bas,
+         const T* __restrict__ vec, T* __restrict__ out)
+{
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  if (r >= npts)
+    return;  // (the whole wave leaves)
+  const int N2 = N * N, Nd = (TD == 3) ? N2 * N : N2;
+  const int32_t* __restrict__ ix = idx + r * Nd;
+  const T* __restrict__ b = bas + r * (TD * N);
+  T acc = T(0);
+  for (int k = lane; k < Nd; k += 64)
+  {
+    T w;
+    if (TD == 3)
+    {
+      const int i0 = k / N2, rem = k - i0 * N2, i1 = rem / N, i2 = rem - i1 * N;
+      w = b[i0] * b[N + i1] * b[2 * N + i2];
+    }
+    else
+    {
+      const int i0 = k / N, i1 = k - i0 * N;
+      w = b[i0] * b[N + i1];
+    }
+    acc += w * vec[ix[k]];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    acc += __shfl_xor(acc, o, 64);
+  if (lane == 0)
+    out[r] = acc;
+}
+
+// ---- phased / apodised source (fus_model_set_source, fusmi.h) ---------------------------------------------------
+// The block kernel and the shared-dof kernels read the source as  gval * bnd_src[k] (+ dgval * bnd_src2[k]).  A source
+// with its own time history per entry keeps those kernels as they are: this kernel evaluates the waveform of
+// source_wave.hpp per boundary entry into the weight arrays they read,
+//   out[k] = base[k] g_k(t),   out2[k] = base2[k] dg_k(t)   (base2 / out2 only where the model has a dg term),
+// for the entries [k0, k1), and the scalars are passed as 1.  base / base2 are the facet weights as the setup left
+// them, amp / tau the per-entry amplitude and delay.  An entry without a source weight (a pure absorbing entry)
+// stores zeros and evaluates nothing.  One thread per entry, every access at k; the waveform in double, rounded
+// to T on store.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_source_entries(int64_t k0, int64_t k1, const T* __restrict__ base, const T* __restrict__ base2,
+                 const T* __restrict__ amp, const T* __restrict__ tau, const SourceWave W, double t,
+                 T* __restrict__ out, T* __restrict__ out2)
+{
+  const int64_t k = k0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= k1)
+    return;
+  const double b = (double)base[k], b2 = base2 ? (double)base2[k] : 0.0;
+  double g = 0.0, dg = 0.0;
+  if (b != 0.0 || b2 != 0.0)
+    source_wave(W, (double)amp[k], t - (double)tau[k], &g, &dg);
+  out[k] = (T)(b * g);
+  if (out2)
+    out2[k] = (T)(b2 * dg);
+}
+
+} // namespace fus
+
+#endif

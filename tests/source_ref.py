@@ -7,7 +7,7 @@ numpy Runge-Kutta loop on ``Problem.K`` and the model vectors of tests/util.py, 
     Lossy    f1 = (K(lin) u + K(att) v + src g(t) + src2 dg(t) - absb v) / m
     Westervelt (vec["mn1"] = M(nlin1) 1, the diagonal of the nonlinear mass term; Westervelt.hpp:246-265):
              f1 = (the Lossy numerator - mn1 v^2) / (m + mn1 u)
-Butcher tables as in fusmi.hip stage_scalars (_linear.py:286-311).  test_source_host.py pins it against the oracle's
+Butcher tables as in wave.hip stage_scalars (_linear.py:286-311).  test_source_host.py pins it against the oracle's
 steppers with the uniform source before anything on the device is compared with it."""
 import numpy as np
 

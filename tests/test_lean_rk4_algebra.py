@@ -1,4 +1,4 @@
-"""The accumulator-free classical RK4 of the fused stage update (kernels.hpp, stage kinds 4-7; fusmi.hip stage_vel)
+"""The accumulator-free classical RK4 of the fused stage update (kernels.hpp, stage kinds 4-7; wave.hip stage_vel)
 restated in numpy on a small random second-order system and compared with the reference's form of the same step
 (Linear.hpp:273-295: accumulators u_, v_ updated at every stage).  Host-side check of the algebra and of the buffer
 rotation the device code uses; the device path itself is compared with the oracle in tests/test_gpu_parity.py."""

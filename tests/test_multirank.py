@@ -101,7 +101,7 @@ def _gloo_worker(rank, size, port, q, start="rest"):
     tags = fa.tag_box_boundary(pr.mesh)
     m, src, absb, coeff = pr.linear_model_vectors(c, rho, tags)
     m, src, absb = (_exchange_sum(dist, rank, pr.V, a) for a in (m, src, absb))
-    # host restatement of the library's stage loop (fusmi.hip stage_begin / stage_end)
+    # host restatement of the library's stage loop (wave.hip stage_begin / stage_end)
     n = pr.ndofs
     off = pr.V.global_offset
     ug, vg = start_state(Problem(orc, N_GLOBAL, P, hi=HI, perturb=0.1), start)
