@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "host.hpp"
+#include "source_signal.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // handles
@@ -73,10 +74,21 @@ struct fus_model
   // the kernels get gval = dgval = 1.  d_src_base / d_src_base2 keep the unmodified weights, d_src_amp / d_src_tau the
   // per-entry amplitude and delay, all in boundary-entry order.  src_tn_int / src_tn_sh: the stage time the block-interior
   // entries [0, nb_int) and the shared entries [nb_int, nb) of d_bsrc hold (NaN: none).
+  // 3: sampled drive signals (fus_model_set_source_signals) -- as 2, with k_source_entries_signal: d_src_chan is the
+  // channel of every entry (-1: silent), renumbered in order of first use along the entry list, d_src_table the samples
+  // time-major, double[nsamp][src_sig.nchan].
   int src_mode = 0;
   void *d_src_base = nullptr, *d_src_base2 = nullptr, *d_src_amp = nullptr, *d_src_tau = nullptr;
+  int32_t* d_src_chan = nullptr;
+  double* d_src_table = nullptr;
+  fus::SourceSignal src_sig{};
   double src_dur = 0.0;
   double src_tn_int = NAN, src_tn_sh = NAN;
+  // The facet weights as the setup produced them, sparse, by ascending internal index (exact in double for both scalar
+  // types): what the entry lists are built from, at setup and again by fus_model_set_source_weights, whose weights
+  // only ever add to the src part.
+  std::vector<int32_t> h_fidx;
+  std::vector<double> h_fsrc, h_fabs, h_fsrc2;
   // c0 and rho0 as fus_model_create was given them, internal cell order: fus_thermal_set_heat_from_monitor forms
   // q_coef = 2 alpha / (rho c) from them
   void *d_c0 = nullptr, *d_rho0 = nullptr;

@@ -214,35 +214,64 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
 // weights (parked in u_) and abs weights (parked in v_) of this rank's own facets
 static void* setup_halo_vector(fus_model* m, int k) { return k == 0 ? m->m : (k == 1 ? m->mn1 : m->v_); }
 
+// A device array of the model's pool: freed and taken off the pool (the entry lists are rebuilt)
+template <typename U>
+static void pool_release(std::vector<void*>& pool, U** p)
+{
+  if (!*p)
+    return;
+  auto it = std::find(pool.begin(), pool.end(), static_cast<void*>(*p));
+  if (it != pool.end())
+    pool.erase(it);
+  (void)hipFree(*p);
+  *p = nullptr;
+}
+
+// The boundary-entry lists: every internal dof with a non-zero source or absorbing weight, sorted by internal index --
+// bidx, nb, nb_int, d_blk_bnd_off, the pseudo pairs appended to d_sh_ptr32 / d_sh_pairs32, d_bnd_mask / d_bnd_base and
+// the weights d_bsrc, d_babs (and d_bsrc2).  Built from the facet weights the setup left (fus_model::h_f*) plus `vol`,
+// the caller's source weights in internal numbering (n_internal long; nullptr: none), which add to the src part only.
+// Lists of an earlier call are freed.  The setup and fus_model_set_source_weights both end here.
 template <typename T>
-static int model_setup_finish(fus_model* m)
+static int model_build_entries(fus_model* m, const T* vol)
 {
   fus_op* op = m->op;
   hipStream_t st = m->ctx->stream;
-  const int64_t n = op->L.n_internal;
-  hipLaunchKernelGGL((k_reciprocal<T>), dim3(nblk(n)), dim3(256), 0, st, n,
-                     static_cast<const T*>(m->m), static_cast<T*>(m->minv));
+  const Layout& L = op->L;
+  const int64_t n = L.n_internal;
   const bool lossy = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
-  std::vector<T> src(n), absb(n), src2(lossy ? n : 0);
-  HIPCHK(hipMemcpyAsync(src.data(), m->u_, n * sizeof(T), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(absb.data(), m->v_, n * sizeof(T), hipMemcpyDeviceToHost, st));
-  if (lossy)
-    HIPCHK(hipMemcpyAsync(src2.data(), m->vn, n * sizeof(T), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   std::vector<int32_t> bidx;
   std::vector<T> bsrc, babs, bsrc2;
-  for (int64_t i = 0; i < n; ++i)
-    if (src[i] != T(0) || absb[i] != T(0) || (lossy && src2[i] != T(0)))
+  {
+    size_t f = 0;
+    const size_t nf = m->h_fidx.size();
+    auto entry = [&](int64_t i, T s, T a, T s2)
     {
-      bidx.push_back((int32_t)i);
-      bsrc.push_back(src[i]);
-      babs.push_back(absb[i]);
+      bidx.push_back((int32_t)i), bsrc.push_back(s), babs.push_back(a);
       if (lossy)
-        bsrc2.push_back(src2[i]);
-    }
+        bsrc2.push_back(s2);
+    };
+    if (!vol)
+      for (; f < nf; ++f)
+        entry(m->h_fidx[f], (T)m->h_fsrc[f], (T)m->h_fabs[f], lossy ? (T)m->h_fsrc2[f] : T(0));
+    else
+      for (int64_t i = 0; i < n; ++i)
+      {
+        const bool facet = f < nf && m->h_fidx[f] == i;
+        if (facet)
+          entry(i, (T)m->h_fsrc[f] + vol[i], (T)m->h_fabs[f], lossy ? (T)m->h_fsrc2[f] : T(0)), ++f;
+        else if (vol[i] != T(0))
+          entry(i, vol[i], T(0), T(0));
+      }
+  }
+  for (int32_t** q : {&m->d_blk_bnd_off, &m->d_sh_ptr32, &m->d_sh_pairs32, &m->d_bnd_base, &m->d_bidx})
+    pool_release(m->allocs, q);
+  pool_release(m->allocs, &m->d_bnd_mask);
+  for (void** q : {&m->d_bsrc, &m->d_babs, &m->d_bsrc2})
+    pool_release(m->allocs, q);
   m->nb = (int64_t)bidx.size();
   {
-    const Layout& L = op->L;
     m->nb_int = std::lower_bound(bidx.begin(), bidx.end(), (int32_t)L.n_int_pad) - bidx.begin();
     std::vector<int32_t> off(L.nblocks + 1);
     for (int32_t b = 0; b < L.nblocks; ++b)
@@ -300,6 +329,36 @@ static int model_setup_finish(fus_model* m)
     FUSCHK(upload(m->allocs, &d_bsrc2, bsrc2, st));
     m->d_bsrc2 = d_bsrc2;
   }
+  HIPCHK(hipStreamSynchronize(st));   // the host vectors leave scope
+  return FUS_OK;
+}
+
+template <typename T>
+static int model_setup_finish(fus_model* m)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t n = op->L.n_internal;
+  hipLaunchKernelGGL((k_reciprocal<T>), dim3(nblk(n)), dim3(256), 0, st, n,
+                     static_cast<const T*>(m->m), static_cast<T*>(m->minv));
+  const bool lossy = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
+  std::vector<T> src(n), absb(n), src2(lossy ? n : 0);
+  HIPCHK(hipMemcpyAsync(src.data(), m->u_, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(absb.data(), m->v_, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  if (lossy)
+    HIPCHK(hipMemcpyAsync(src2.data(), m->vn, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  m->h_fidx.clear(), m->h_fsrc.clear(), m->h_fabs.clear(), m->h_fsrc2.clear();
+  for (int64_t i = 0; i < n; ++i)
+    if (src[i] != T(0) || absb[i] != T(0) || (lossy && src2[i] != T(0)))
+    {
+      m->h_fidx.push_back((int32_t)i);
+      m->h_fsrc.push_back((double)src[i]);
+      m->h_fabs.push_back((double)absb[i]);
+      if (lossy)
+        m->h_fsrc2.push_back((double)src2[i]);
+    }
+  FUSCHK(model_build_entries<T>(m, nullptr));
   HIPCHK(hipMemsetAsync(m->u_, 0, n * sizeof(T), st));
   HIPCHK(hipMemsetAsync(m->v_, 0, n * sizeof(T), st));
   HIPCHK(hipMemsetAsync(m->vn, 0, n * sizeof(T), st));
@@ -431,7 +490,7 @@ static StageArgs<T> stage_args(fus_model* m, int i, const StageScalars& sc)
   return S;
 }
 
-// Per-entry source (src_mode 2): the weight arrays of the entries [k0, k1) for the stage time tn.  The rule of the
+// Per-entry source (src_mode 2, and 3 with the sampled signals): the weight arrays of the entries [k0, k1) for the stage time tn.  The rule of the
 // callers: before a kernel reads a range of d_bsrc / d_bsrc2, the range holds the values for the time whose scalar
 // that kernel would have carried -- the block kernel and k_boundary_partial the stage's own time, the shared-dof and
 // interface stage kernels (BndNext) the next stage's.
@@ -441,12 +500,23 @@ static int source_entries(fus_model* m, int64_t k0, int64_t k1, double tn)
   if (k1 <= k0)
     return FUS_OK;
   const bool lossy = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
-  const SourceWave W = source_wave_make(m->freq, m->amp, m->speed, (lossy && m->forms == 0) ? 2.0 : 1.0, m->src_dur);
-  ProfScope ps(m->ctx, "source");
-  hipLaunchKernelGGL((k_source_entries<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
-                     static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
-                     static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), W, tn,
-                     static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+  if (m->src_mode == 3)
+  {
+    ProfScope ps(m->ctx, "source_signal");
+    hipLaunchKernelGGL((k_source_entries_signal<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
+                       static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
+                       static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), m->d_src_chan,
+                       m->d_src_table, m->src_sig, tn, static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+  }
+  else
+  {
+    const SourceWave W = source_wave_make(m->freq, m->amp, m->speed, (lossy && m->forms == 0) ? 2.0 : 1.0, m->src_dur);
+    ProfScope ps(m->ctx, "source");
+    hipLaunchKernelGGL((k_source_entries<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
+                       static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
+                       static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), W, tn,
+                       static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+  }
   HIPCHK(hipGetLastError());
   if (k0 == 0)
     m->src_tn_int = tn;
@@ -482,7 +552,7 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   // boundary terms of the shared boundary dofs: a launch of their own unless the previous stage left them (below)
   const int64_t nbs = m->nb - m->nb_int;
   const bool bnd_launch = nbs > 0 && !(m->bnd_valid && op->bnd_owner == m && m->bnd_tn == sc_now.tn);
-  if (m->src_mode == 2)
+  if (m->src_mode >= 2)   // 2: the analytic waveform per entry, 3: sampled signals
   {
     // the source rides in the weights: the block-interior entries for this stage's time, the shared ones too when
     // k_boundary_partial reads them; in the steady RK4 state the previous stage_end has left both
@@ -566,7 +636,7 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     B.partial = static_cast<T*>(op->d_partial);
     m->bnd_valid = true, m->bnd_tn = scn.tn;
     op->bnd_owner = m;
-    if (m->src_mode == 2)
+    if (m->src_mode >= 2)
     {
       // the kernels below read the shared entries for the next stage's time; the same launch leaves the
       // block-interior entries for the next stage's block kernel (this stage's has run: same stream)
@@ -730,6 +800,16 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
 }
 
 // ---- phased / apodised source (fusmi.h) ----
+// the channel list and the sample table of the sampled signals
+static void signal_free(fus_model* m)
+{
+  if (m->d_src_chan)
+    (void)hipFree(m->d_src_chan);
+  if (m->d_src_table)
+    (void)hipFree(m->d_src_table);
+  m->d_src_chan = nullptr, m->d_src_table = nullptr;
+}
+
 static void source_free(fus_model* m)
 {
   for (void** q : {&m->d_src_base, &m->d_src_base2, &m->d_src_amp, &m->d_src_tau})
@@ -738,6 +818,7 @@ static void source_free(fus_model* m)
       (void)hipFree(*q);
     *q = nullptr;
   }
+  signal_free(m);
 }
 
 template <typename T>
@@ -815,6 +896,7 @@ static int model_set_source(fus_model* m, const void* amplitude, const void* del
     amp[k] = a, tau[k] = td;
   }
   // from here on the model changes
+  signal_free(m);   // (leaving the sampled signals, if they were on)
   if (!m->d_src_base)
   {
     HIPCHK(hipMalloc(&m->d_src_base, std::max<size_t>(bytes, 16)));
@@ -854,6 +936,167 @@ static int model_set_source(fus_model* m, const void* amplitude, const void* del
     m->src_mode = 2, m->src_dur = duration;
   }
   changed();
+  return FUS_OK;
+}
+
+// ---- source weights at any dof (fus_model_set_source_weights, fusmi.h) ----
+template <typename T>
+static int model_set_source_weights(fus_model* m, const void* weights, int space)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<T> vol;
+  if (weights)
+  {
+    std::vector<T> hbuf;
+    const T* w = static_cast<const T*>(weights);
+    if (space == FUS_DEVICE)
+    {
+      hbuf.resize(op->ndofs);
+      HIPCHK(hipMemcpyAsync(hbuf.data(), weights, (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      w = hbuf.data();
+    }
+    for (int64_t d = 0; d < op->ndofs; ++d)
+      if (!std::isfinite((double)w[d]))
+        return fail(FUS_ERR_ARG, "fus_model_set_source_weights: non-finite weight at dof " + std::to_string(d));
+    vol.assign(op->L.n_internal, T(0));
+    for (int64_t d = 0; d < op->ndofs; ++d)
+      vol[op->L.dof_perm[d]] = w[d];
+  }
+  // from here on the model changes: the default source function on the new entry lists
+  source_free(m);
+  m->src_mode = 0, m->src_dur = 0.0;
+  FUSCHK(model_build_entries<T>(m, weights ? vol.data() : nullptr));
+  m->bnd_valid = false, m->gsteps = 0;
+  m->src_tn_int = m->src_tn_sh = NAN;
+  return FUS_OK;
+}
+
+// ---- sampled drive signals (fus_model_set_source_signals, fusmi.h) ----
+template <typename T>
+static int model_set_source_signals(fus_model* m, int64_t nchan, int64_t nsamp, double t_first, double ds,
+                                    const double* signals, const int32_t* channel, const void* amplitude,
+                                    const void* delay, int space)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t nb = m->nb;
+  const size_t bytes = (size_t)nb * sizeof(T);
+  HIPCHK(hipStreamSynchronize(st));
+  auto copy = [&](void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) -> int
+  {
+    HIPCHK(hipMemcpyAsync(dst, src, nbytes, kind, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FUS_OK;
+  };
+  for (int64_t i = 0; i < nchan * nsamp; ++i)
+    if (!std::isfinite(signals[i]))
+      return fail(FUS_ERR_ARG, "fus_model_set_source_signals: non-finite sample " + std::to_string(i % nsamp) + " of channel "
+                                   + std::to_string(i / nsamp));
+  // the source weights and the entries' internal indices, as the setup (or fus_model_set_source_weights) left them
+  std::vector<int32_t> bidx(nb);
+  std::vector<T> base(nb), base2(m->d_bsrc2 ? nb : 0);
+  if (nb > 0)
+  {
+    FUSCHK(copy(bidx.data(), m->d_bidx, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FUSCHK(copy(base.data(), m->d_src_base ? m->d_src_base : m->d_bsrc, bytes, hipMemcpyDeviceToHost));
+    if (m->d_bsrc2)
+      FUSCHK(copy(base2.data(), m->d_src_base2 ? m->d_src_base2 : m->d_bsrc2, bytes, hipMemcpyDeviceToHost));
+  }
+  std::vector<T> hbuf[2];
+  const T* h[2] = {static_cast<const T*>(amplitude), static_cast<const T*>(delay)};
+  for (int j = 0; j < 2; ++j)
+    if (h[j] && space == FUS_DEVICE)
+    {
+      hbuf[j].resize(op->ndofs);
+      FUSCHK(copy(hbuf[j].data(), h[j], (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost));
+      h[j] = hbuf[j].data();
+    }
+  // gather through dof_perm into entry order; only the entries with a source weight count.  The channels are
+  // renumbered in order of first use along the entry list (k_source_entries_signal: rows read contiguously)
+  std::vector<int32_t> caller(op->L.n_internal, -1);
+  for (int64_t d = 0; d < op->ndofs; ++d)
+    caller[op->L.dof_perm[d]] = (int32_t)d;
+  std::vector<T> amp(nb, T(0)), tau(nb, T(0));
+  std::vector<int32_t> chan(nb, -1), renum(nchan, -1), used;
+  for (int64_t k = 0; k < nb; ++k)
+  {
+    if (base[k] == T(0) && (base2.empty() || base2[k] == T(0)))
+      continue;
+    const int32_t d = caller[bidx[k]];
+    const T a = h[0] ? h[0][d] : T(1), td = h[1] ? h[1][d] : T(0);
+    if (!std::isfinite((double)a) || a < T(0) || !std::isfinite((double)td) || td < T(0))
+      return fail(FUS_ERR_ARG, "fus_model_set_source_signals: negative or non-finite amplitude / delay at dof "
+                                   + std::to_string(d) + " of the source");
+    const int32_t c = channel ? channel[d] : 0;
+    if (c < -1 || c >= nchan)
+      return fail(FUS_ERR_ARG, "fus_model_set_source_signals: channel " + std::to_string(c) + " at dof " + std::to_string(d)
+                                   + " is neither -1 nor in [0, nchan)");
+    amp[k] = a, tau[k] = td;
+    if (c < 0)
+      continue;
+    if (renum[c] < 0)
+      renum[c] = (int32_t)used.size(), used.push_back(c);
+    chan[k] = renum[c];
+  }
+  const int64_t ncu = std::max<int64_t>((int64_t)used.size(), 1);
+  std::vector<double> table((size_t)ncu * nsamp, 0.0);
+  for (size_t c = 0; c < used.size(); ++c)
+    for (int64_t j = 0; j < nsamp; ++j)
+      table[(size_t)j * ncu + c] = signals[(size_t)used[c] * nsamp + j];
+  // the new arrays first: a failed allocation leaves the source as it was
+  void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // table, chan, base, base2, amp, tau
+  const size_t want[6] = {table.size() * sizeof(double), (size_t)nb * sizeof(int32_t),
+                          m->d_src_base ? 0 : bytes, (m->d_src_base || !m->d_bsrc2) ? 0 : bytes,
+                          m->d_src_amp ? 0 : bytes, m->d_src_tau ? 0 : bytes};
+  const bool need[6] = {true, true, !m->d_src_base, !m->d_src_base && m->d_bsrc2, !m->d_src_amp, !m->d_src_tau};
+  for (int j = 0; j < 6; ++j)
+  {
+    if (!need[j])
+      continue;
+    const hipError_t e = hipMalloc(&fresh[j], std::max<size_t>(want[j], 16));
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      for (int i = 0; i < j; ++i)
+        if (fresh[i])
+          (void)hipFree(fresh[i]);
+      return fail(FUS_ERR_HIP, "fus_model_set_source_signals: cannot allocate " + std::to_string(std::max<size_t>(want[j], 16))
+                                   + " bytes" + (j == 0 ? " of sample table: " : ": ") + hipGetErrorString(e));
+    }
+  }
+  // from here on the model changes
+  signal_free(m);
+  m->d_src_table = static_cast<double*>(fresh[0]), m->d_src_chan = static_cast<int32_t*>(fresh[1]);
+  if (need[2])
+  {
+    m->d_src_base = fresh[2];
+    if (nb > 0)
+      FUSCHK(copy(m->d_src_base, m->d_bsrc, bytes, hipMemcpyDeviceToDevice));
+  }
+  if (need[3])
+  {
+    m->d_src_base2 = fresh[3];
+    if (nb > 0)
+      FUSCHK(copy(m->d_src_base2, m->d_bsrc2, bytes, hipMemcpyDeviceToDevice));
+  }
+  if (need[4])
+    m->d_src_amp = fresh[4];
+  if (need[5])
+    m->d_src_tau = fresh[5];
+  FUSCHK(copy(m->d_src_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (nb > 0)
+  {
+    FUSCHK(copy(m->d_src_chan, chan.data(), (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice));
+    FUSCHK(copy(m->d_src_amp, amp.data(), bytes, hipMemcpyHostToDevice));
+    FUSCHK(copy(m->d_src_tau, tau.data(), bytes, hipMemcpyHostToDevice));
+  }
+  m->src_sig = SourceSignal{t_first, ds, nsamp, ncu};
+  m->src_mode = 3, m->src_dur = 0.0;
+  m->bnd_valid = false, m->gsteps = 0;
+  m->src_tn_int = m->src_tn_sh = NAN;
   return FUS_OK;
 }
 
@@ -1522,6 +1765,33 @@ int fus_model_set_source(fus_model* m, const void* amplitude, const void* delay,
     return fail(FUS_ERR_STATE, "fus_model_set_source: the model's setup is not finished");
   HIPCHK(hipSetDevice(m->ctx->device));
   return FUS_BY_DTYPE(m->op->dtype, model_set_source, m, amplitude, delay, duration, space);
+}
+
+int fus_model_set_source_weights(fus_model* m, const void* weights, int space)
+{
+  if (!m || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_model_set_source_weights: bad model or space");
+  if (!m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_set_source_weights: the model's setup is not finished");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  return FUS_BY_DTYPE(m->op->dtype, model_set_source_weights, m, weights, space);
+}
+
+int fus_model_set_source_signals(fus_model* m, int64_t nchan, int64_t nsamp, double t_first, double ds,
+                                 const double* signals, const int32_t* channel, const void* amplitude,
+                                 const void* delay, int space)
+{
+  if (!m || (space != FUS_HOST && space != FUS_DEVICE) || !signals || nchan < 1 || (!channel && nchan != 1))
+    return fail(FUS_ERR_ARG, "fus_model_set_source_signals: bad model, space, signals or channel (NULL only with nchan == 1)");
+  if (!source_signal_ok(nsamp, t_first, ds))
+    return fail(FUS_ERR_ARG, "fus_model_set_source_signals: nsamp >= 2, ds > 0 and t_first finite are required");
+  if (nchan > INT32_MAX || nsamp > INT64_MAX / (int64_t)sizeof(double) / nchan)
+    return fail(FUS_ERR_ARG, "fus_model_set_source_signals: nchan * nsamp * 8 bytes exceed the address range");
+  if (!m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_set_source_signals: the model's setup is not finished");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  return FUS_BY_DTYPE(m->op->dtype, model_set_source_signals, m, nchan, nsamp, t_first, ds, signals, channel, amplitude,
+                      delay, space);
 }
 
 int fus_model_get_mass(fus_model* m, void* out)

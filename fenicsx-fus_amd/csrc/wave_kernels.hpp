@@ -5,6 +5,7 @@
 #define FUS_WAVE_KERNELS_HPP
 
 #include "kernels.hpp"
+#include "source_signal.hpp"
 #include "source_wave.hpp"
 
 namespace fus
@@ -358,6 +359,36 @@ k_source_entries(int64_t k0, int64_t k1, const T* __restrict__ base, const T* __
   double g = 0.0, dg = 0.0;
   if (b != 0.0 || b2 != 0.0)
     source_wave(W, (double)amp[k], t - (double)tau[k], &g, &dg);
+  out[k] = (T)(b * g);
+  if (out2)
+    out2[k] = (T)(b2 * dg);
+}
+
+// ---- sampled drive signals (fus_model_set_source_signals, fusmi.h) ----------------------------------------------
+// The sibling of k_source_entries for a source whose time history is a table of samples: the same range [k0, k1),
+// the same out / out2 and the same rule about the time a range holds; g_k(t) = amp[k] S_c(t - tau[k]) with
+// c = chan[k] and S_c the cubic of source_signal.hpp.  An entry without a source weight or with channel -1 stores
+// zeros and reads no sample.  One thread per entry, every per-entry access at k.
+// The table is time-major, double[nsamp][nchan], and the channels are numbered in order of first use along the entry
+// list (the host renumbers them): the 64 entries of a wavefront that drive one channel each with equal delays (a
+// time-reversal mirror) read four contiguous 512-byte rows; with a few channels over many entries (element groups)
+// the lanes of a row hit the same few cache lines and the whole table stays in L2.  The segment index depends on the
+// entry's delay, so it is a vector value and the samples come through vector loads.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_source_entries_signal(int64_t k0, int64_t k1, const T* __restrict__ base, const T* __restrict__ base2,
+                        const T* __restrict__ amp, const T* __restrict__ tau, const int32_t* __restrict__ chan,
+                        const double* __restrict__ table, const SourceSignal P, double t, T* __restrict__ out,
+                        T* __restrict__ out2)
+{
+  const int64_t k = k0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= k1)
+    return;
+  const double b = (double)base[k], b2 = base2 ? (double)base2[k] : 0.0;
+  const int32_t c = chan[k];
+  double g = 0.0, dg = 0.0;
+  if ((b != 0.0 || b2 != 0.0) && c >= 0)
+    source_signal(P, table, c, (double)amp[k], t - (double)tau[k], &g, &dg);
   out[k] = (T)(b * g);
   if (out2)
     out2[k] = (T)(b2 * dg);

@@ -219,6 +219,43 @@ class _SpectralExplicit:
         """Back to the default source: the same g(t) at every DOF of the source boundary."""
         check(lib().fus_model_set_source(self.h, None, None, C.c_double(0.0), C.c_int(_abi.FUS_HOST)))
 
+    # ---- sources anywhere in the mesh, sampled drive signals (fusmi.h) ----
+    def set_source_weights(self, w):
+        """Give every DOF a source weight of its own (array or Function over the model's space, either sign): DOF d
+        gains the right-hand-side term ``w[d] * g_d(t)`` with the model's source function, on top of the facet weight
+        where d lies on the source boundary (:func:`fenicsxfus_amd.source.point_weights` for point sources).  Replaces
+        earlier weights and puts the source function back to the default -- call :meth:`set_source` /
+        :meth:`set_source_signals` afterwards; ``None`` removes the weights."""
+        a = None if w is None else np.ascontiguousarray(_array(w), dtype=self.data.dtype)
+        if a is not None and a.shape != (self.data.ndofs,):
+            raise _abi.FusError(f"set_source_weights: expected {self.data.ndofs} values, one per DOF, got shape {a.shape}")
+        check(lib().fus_model_set_source_weights(self.h, ptr(a), C.c_int(_abi.FUS_HOST)))
+
+    def set_source_signals(self, signals, ds: float, t_first: float = 0.0, channel=None, amplitude=None, delay=None):
+        """Drive the source with sampled signals: ``signals`` [nchan, nsamp] (or [nsamp]) holds samples at the times
+        ``t_first + j * ds``, ``channel`` [ndofs] names the row each DOF plays (-1: silent; ``None`` with one channel:
+        that channel everywhere), interpolated with the C1 cubic of :func:`fenicsxfus_amd.source.signal_value`; DOF d
+        with a source weight emits ``amplitude[d] * S(t - delay[d])``.  The signal stands in for the whole default
+        waveform (``source.waveform(..., scale=)`` produces such samples).  :meth:`clear_source` leaves this mode."""
+        s = np.ascontiguousarray(np.atleast_2d(np.asarray(signals, dtype=np.float64)))
+        if s.ndim != 2:
+            raise _abi.FusError(f"set_source_signals: signals must be [nchan, nsamp], got shape {s.shape}")
+        nchan, nsamp = s.shape
+        if channel is None:
+            if nchan != 1:
+                raise _abi.FusError("set_source_signals: channel=None needs exactly one channel")
+            ch = None
+        else:
+            ch = np.ascontiguousarray(np.asarray(channel), dtype=np.int32)
+            if ch.shape != (self.data.ndofs,):
+                raise _abi.FusError(f"set_source_signals: expected {self.data.ndofs} channels, one per DOF, got shape {ch.shape}")
+        a, d = (None if x is None else np.ascontiguousarray(_array(x), dtype=self.data.dtype) for x in (amplitude, delay))
+        for x in (a, d):
+            if x is not None and x.shape != (self.data.ndofs,):
+                raise _abi.FusError(f"set_source_signals: expected {self.data.ndofs} values, one per DOF, got shape {x.shape}")
+        check(lib().fus_model_set_source_signals(self.h, C.c_int64(nchan), C.c_int64(nsamp), C.c_double(t_first),
+                                                 C.c_double(ds), ptr(s), ptr(ch), ptr(a), ptr(d), C.c_int(_abi.FUS_HOST)))
+
     def u_sol(self):
         self._pull()
         return self.u_n

@@ -354,6 +354,63 @@ int fus_model_monitor_info(fus_model* model, int64_t* nsamples, double* t_first,
  * every sharer of a DOF passes the same values for it (they are functions of position). */
 int fus_model_set_source(fus_model* model, const void* amplitude, const void* delay, double duration, int space);
 
+/* ---- sources anywhere in the mesh: a source weight at any DOF -----------------------------------------------------
+ * By default a DOF radiates only if it lies on a tag-1 boundary facet.  This call gives every DOF d a source weight
+ * w_d of its own: its right-hand side gains  w_d g_d(t),  g_d the source function the model has (the default one,
+ * fus_model_set_source's or fus_model_set_source_signals') -- exactly the term a tag-1 entry receives for its facet
+ * weight.  A DOF that is also on the source boundary radiates with  facet weight + w_d.  The dg term of FUS_LOSSY /
+ * FUS_WESTERVELT keeps the facet part only: a volume source s on the right of
+ *   (1/(rho c^2)) p_tt - div((1/rho) grad p) - div((delta/(rho c^2)) grad p_t) = s
+ * enters through the src term alone.  Units are the caller's:  w_d = s(x_d) (M(1) 1)_d  is a distributed source s under
+ * GLL quadrature;  w_d = q phi_d(x0)  a point source of strength q at x0, phi_d(x0) the Lagrange basis values at the
+ * located point (the transpose of what fus_model_sample evaluates).
+ *   weights   T[ndofs] in caller numbering, host or device memory (`space`); finite, of either sign.  A non-finite value
+ *             -> FUS_ERR_ARG, the model stays as it was.  NULL removes the weights: the model then computes, bit for bit,
+ *             what a model that never had any computes.
+ * Every call replaces the earlier weights (they do not accumulate) and puts amplitude / delay / duration / signals back
+ * to the default source: set the weights first, then fus_model_set_source or fus_model_set_source_signals.  Legal once
+ * the model's setup is finished (FUS_ERR_STATE before) and between steps; the state, the receivers and the monitor are
+ * kept.  Cost: the call rebuilds the model's list of boundary entries on the host (every DOF with a source or absorbing
+ * weight); no kernel changes, a step enqueues the same launches, and each weighted DOF costs what a boundary DOF costs.
+ * Several ranks: each rank passes its own share of an interface DOF's weight (the shares of the sharers sum to the
+ * source; the weight of a point source comes from the one rank whose cell was located), as each rank's facet term
+ * rides in its own partial sum. */
+int fus_model_set_source_weights(fus_model* model, const void* weights, int space);
+
+/* ---- sampled drive signals: the source plays back tables of samples -----------------------------------------------
+ * Instead of the windowed cosine, a DOF d with a source weight (facet weight and / or fus_model_set_source_weights')
+ * and channel c = channel[d] >= 0 is driven by
+ *   g_d(t)  = a_d S_c(t - tau_d)
+ *   dg_d(t) = a_d S_c'(t - tau_d)                                 (the dg term of FUS_LOSSY / FUS_WESTERVELT)
+ * S_c the cubic (Catmull-Rom) interpolant of the samples signals[c][j] at the times t_first + j ds: with
+ * x = (t - t_first) / ds, j = floor(x), u = x - j, segment j uses the samples j-1 .. j+2, samples outside [0, nsamp)
+ * counting as 0,
+ *   S_c  = w_0 s_{j-1} + w_1 s_j + w_2 s_{j+1} + w_3 s_{j+2}
+ *   w_0 = (-u + 2u^2 - u^3) / 2,  w_1 = (2 - 5u^2 + 3u^3) / 2,  w_2 = (u + 4u^2 - 3u^3) / 2,  w_3 = (-u^2 + u^3) / 2
+ * and S_c' is the analytic derivative of the same cubic.  S_c passes through the samples, is C^1 on its support and
+ * S_c = S_c' = 0 exactly before t_first - ds and after t_first + nsamp ds (start and end the signals at 0 and S_c is
+ * C^1 everywhere).  There is no hidden factor: the signal stands in for the whole  C W(s) cos(w0 s)  of the default
+ * source, including the scale = 2 of FUS_LOSSY / FUS_WESTERVELT with option "forms" = 0.  Evaluated in double for both
+ * scalar types at the stage time the default source uses, rounded to T with the weight.
+ *   nchan, nsamp       channels and samples per channel; nsamp >= 2
+ *   t_first, ds        time of sample 0 and sample spacing, ds > 0
+ *   signals            host, double[nchan][nsamp]; finite
+ *   channel            host, int32[ndofs] in caller numbering, -1 = silent; NULL (only with nchan == 1) = channel 0
+ *                      everywhere.  Values at DOFs without a source weight are ignored
+ *   amplitude, delay   as in fus_model_set_source
+ * Errors: those of fus_model_set_source, and channel[d] >= nchan (or < -1) at a DOF with a source weight, nsamp < 2,
+ * ds <= 0, a non-finite sample -> FUS_ERR_ARG; the model stays as it was.  The table takes at most nchan nsamp 8 bytes
+ * of device memory (channels no DOF uses are left out); if it cannot be allocated -> FUS_ERR_HIP naming the bytes, the
+ * source stays as it was.  A successful fus_model_set_source (any arguments) leaves signal mode and frees the table.
+ * Samples such as fenicsxfus_amd.source.waveform(..., scale=) produces reproduce the analytic source.  Cost: as the
+ * per-entry source of fus_model_set_source, one small kernel launch per new stage time -- profile name "source_signal"
+ * -- reading four samples per entry.  Legal once the model's setup is finished (FUS_ERR_STATE before) and between
+ * steps; the state is kept.  Several ranks: every sharer of a DOF passes the same channel, amplitude and delay for it
+ * and the same samples for that channel. */
+int fus_model_set_source_signals(fus_model* model, int64_t nchan, int64_t nsamp, double t_first, double ds,
+                                 const double* signals, const int32_t* channel, const void* amplitude, const void* delay,
+                                 int space);
+
 /* ---- bioheat: Pennes equation and CEM43 thermal dose on the operator's mesh ---------------------------------------
  * What a focused-ultrasound user computes from the pressure maps: the temperature rise the beam causes and the thermal
  * dose it leaves.  (The reference has no thermal model; this section replaces nothing there.)
@@ -572,7 +629,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the library's own kernels on the stream they run on.  Names:
  * "stiffness" (block operator kernel), "shared" (shared-DOF reduction), "stage" (fused RK stage
- * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform),
+ * update), "boundary", "halo", "monitor" (field-monitor sample), "source" (per-entry source waveform), "source_signal" (the
+ * same for sampled drive signals),
  * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared"), "thermal_sts" (the
  * same for a super-time-stepping stage), "thermal_bc" (convective surface term, once per operator application of a
  * bioheat object with convective DOFs), "thermal_fix" (writes of the fixed values), "thermal_if" (bioheat stage update of

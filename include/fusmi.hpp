@@ -293,6 +293,16 @@ public:
   {
     check(fus_model_set_source(h_, amp, delay, duration, FUS_HOST));
   }
+  // source weight at any DOF (fusmi.h): w (T[ndofs], caller numbering) adds w_d g_d(t) to DOF d's right-hand side;
+  // replaces earlier weights and restores the default source function, nullptr removes them
+  void set_source_weights(const T* w) { check(fus_model_set_source_weights(h_, w, FUS_HOST)); }
+  // sampled drive signals (fusmi.h): signals [nchan][nsamp] at the times t_first + j ds, cubic interpolation; channel
+  // (int32[ndofs], -1 = silent; nullptr with nchan == 1: channel 0 everywhere); amplitude and delay as in set_source
+  void set_source_signals(std::int64_t nchan, std::int64_t nsamp, double t_first, double ds, const double* signals,
+                          const std::int32_t* channel = nullptr, const T* amp = nullptr, const T* delay = nullptr)
+  {
+    check(fus_model_set_source_signals(h_, nchan, nsamp, t_first, ds, signals, channel, amp, delay, FUS_HOST));
+  }
   fus_model* handle() const { return h_; }
   ~SpectralModel() { fus_model_destroy(h_); }
   SpectralModel(const SpectralModel&) = delete;
