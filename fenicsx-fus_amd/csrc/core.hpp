@@ -13,10 +13,153 @@
 #include "source_signal.hpp"
 
 // -------------------------------------------------------------------------------------------------
+// owners of device memory
+// -------------------------------------------------------------------------------------------------
+// (The types below are FUS_HIDDEN: their inline members stay out of the library's dynamic symbols.)
+// One device allocation and its owner: move-only, the destructor frees.  The rule of the units stays the caller's: the
+// device is current, and the model's stream synchronised, before a buffer that a kernel may still read is reset, replaced
+// or destroyed.
+struct FUS_HIDDEN DevBuf
+{
+  void* p = nullptr;
+  size_t bytes = 0;   // as asked for (the allocation itself is never shorter than 16 bytes)
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept
+  {
+    if (this != &o)
+    {
+      reset();
+      p = o.p, bytes = o.bytes;
+      o.p = nullptr, o.bytes = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset()
+  {
+    if (p)
+      (void)hipFree(p);
+    p = nullptr, bytes = 0;
+  }
+  explicit operator bool() const { return p != nullptr; }
+  template <typename U>
+  U* as() const
+  {
+    return static_cast<U*>(p);
+  }
+  // replaces what the buffer held by n bytes, uninitialised; a failure leaves it empty and the runtime without a sticky error
+  int alloc(size_t n, const char* what)
+  {
+    reset();
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 16));
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      p = nullptr;
+      return fail(FUS_ERR_HIP, "cannot allocate " + std::to_string(n) + " bytes of " + what + ": " + hipGetErrorString(e));
+    }
+    bytes = n;
+    return FUS_OK;
+  }
+};
+template <typename U>
+static int upload(DevBuf& b, const std::vector<U>& v, hipStream_t st, const char* what)
+{
+  FUSCHK(b.alloc(v.size() * sizeof(U), what));
+  if (!v.empty())
+    HIPCHK(hipMemcpyAsync(b.p, v.data(), b.bytes, hipMemcpyHostToDevice, st));
+  return FUS_OK;
+}
+
+// The arrays a model allocates once, at setup or on the first use of a feature: freed with the model (dalloc,
+// dalloc_bytes and upload below take it like the std::vector<void*> of fus_op::allocs)
+struct FUS_HIDDEN DevPool : std::vector<void*>
+{
+  DevPool() = default;
+  DevPool(const DevPool&) = delete;
+  DevPool& operator=(const DevPool&) = delete;
+  ~DevPool()
+  {
+    for (void* q : *this)
+      (void)hipFree(q);
+  }
+};
+
+// -------------------------------------------------------------------------------------------------
 // handles
 // -------------------------------------------------------------------------------------------------
-// Of the wave model the bioheat unit reads what its two heat-load calls need: op, d_rho0, d_c0 and the monitor's d_mon,
-// mon_n, mon_nharm, mon_every, mon_which.
+// The parts of fus_model that a call between runs replaces as a whole.  Every array in them is a DevBuf, so a part is
+// rebuilt beside the one in force and move-assigned once nothing can fail any more.
+
+// The boundary-entry lists (model_build_entries, wave.hip): the dofs with a diagonal source / absorbing weight, sorted
+// by internal index: [0, nb_int) are block-interior (applied in the fused epilogue through d_blk_bnd_off), [nb_int, nb)
+// are shared dofs (their terms ride in pseudo partial slots: boundary_next / k_boundary_partial)
+struct FUS_HIDDEN ModelEntries
+{
+  int64_t nb = 0, nb_int = 0;
+  DevBuf d_bidx, d_blk_bnd_off;    // int32
+  DevBuf d_sh_ptr32, d_sh_pairs32; // int32: shared CSR incl. boundary pseudo pairs
+  DevBuf d_bnd_mask;               // uint64, rank-local shared dofs: boundary dof bits ...
+  DevBuf d_bnd_base;               // int32 ... and boundary dofs ahead of each 64-dof word (both empty without such dofs)
+  DevBuf d_bsrc, d_babs;           // T: the weights the kernels read
+  DevBuf d_bsrc2;                  // T, lossy: delta/(rho c^2) w_f on the source facets (dg term); empty otherwise
+};
+
+// phased / apodised source (fus_model_set_source).  mode 0: the default source, d_bsrc / d_bsrc2 hold the facet weights.
+// 1: amplitude only -- the weights times the per-entry amplitude, folded in once; the scalar path stays.
+// 2: delays or a burst -- k_source_entries writes d_bsrc / d_bsrc2 = weights x per-entry waveform for a stage time and
+// the kernels get gval = dgval = 1.  d.base / d.base2 keep the unmodified weights, d.amp / d.tau the per-entry amplitude
+// and delay, all in boundary-entry order.  tn_int / tn_sh: the stage time the block-interior entries [0, nb_int) and the
+// shared entries [nb_int, nb) of d_bsrc hold (NaN: none).
+// 3: sampled drive signals (fus_model_set_source_signals) -- as 2, with k_source_entries_signal: d.chan is the channel
+// of every entry (-1: silent), renumbered in order of first use along the entry list, d.table the samples time-major,
+// double[nsamp][sig.nchan].
+struct FUS_HIDDEN ModelSource
+{
+  int mode = 0;
+  double dur = 0.0;
+  struct Arrays
+  {
+    DevBuf base, base2, amp, tau;   // T
+    DevBuf chan;                    // int32
+    DevBuf table;                   // double
+  } d;
+  fus::SourceSignal sig{};
+  double tn_int = NAN, tn_sh = NAN;
+  // The facet weights as the setup produced them, sparse, by ascending internal index (exact in double for both scalar
+  // types): what the entry lists are built from, at setup and again by fus_model_set_source_weights, whose weights
+  // only ever add to the src part.
+  std::vector<int32_t> h_fidx;
+  std::vector<double> h_fsrc, h_fabs, h_fsrc2;
+};
+
+// receivers (fus_model_set_receivers): per point the internal indices of its cell's dofs and the 1-D basis values at its
+// reference coordinates; record buffer for sampling every k steps inside the RK loops
+struct FUS_HIDDEN ModelReceivers
+{
+  int64_t n = 0;
+  DevBuf d_idx;          // int32
+  DevBuf d_bas, d_out;   // T
+  DevBuf d_rec;          // T: it only grows, until new receivers drop it
+  int rec_every = 0, rec_which = 0;
+  int64_t rec_cap = 0, rec_n = 0, rec_step = 0;  // rec_cap: the records the last fus_model_record asked for
+  std::vector<double> rec_times;
+};
+
+// field monitor (fus_model_monitor): per-DOF accumulator planes over the internal vector, one allocation --
+// T[2][n_internal] (max, min) then double[2 + 2 nharm][n_internal] (sum, sum of squares, cos_k, sin_k)
+struct FUS_HIDDEN ModelMonitor
+{
+  DevBuf d_mon;
+  int every = 0, which = 0, nharm = 0;
+  double freq = 0.0;
+  int64_t skip = 0, count = 0, step = 0, n = 0;
+  double t_first = 0.0, t_last = 0.0;
+};
+
+// Of the wave model the bioheat unit reads what its two heat-load calls need: op, d_rho0, d_c0 and the monitor's
+// mon.d_mon, mon.n, mon.nharm, mon.every, mon.which.
 struct fus_model
 {
   fus_ctx* ctx;
@@ -27,19 +170,8 @@ struct fus_model
   double freq, amp, speed;
   void *u0 = nullptr, *v0 = nullptr, *u_ = nullptr, *v_ = nullptr, *un = nullptr, *vn = nullptr,
        *b = nullptr, *minv = nullptr, *m = nullptr, *coef = nullptr, *coef2 = nullptr;
-  void* d_bsrc2 = nullptr;  // lossy: delta/(rho c^2) w_f on the source facets (dg term)
   void* mn1 = nullptr;      // Westervelt: diag of M(-2 beta/(rho^2 c^4)), internal numbering
-  // boundary dofs (diagonal source / absorbing weights), sorted by internal index:
-  // [0, nb_int) are block-interior (applied in the fused epilogue through d_blk_bnd_off),
-  // [nb_int, nb) are shared dofs (their terms ride in pseudo partial slots: boundary_next / k_boundary_partial)
-  int64_t nb = 0, nb_int = 0;
-  int32_t* d_bidx = nullptr;
-  int32_t* d_blk_bnd_off = nullptr;
-  int32_t *d_sh_ptr32 = nullptr, *d_sh_pairs32 = nullptr;  // shared CSR incl. boundary pseudo pairs
-  uint64_t* d_bnd_mask = nullptr;                           // rank-local shared dofs: boundary dof bits ...
-  int32_t* d_bnd_base = nullptr;                            // ... and boundary dofs ahead of each 64-dof word
-  void *d_bsrc = nullptr, *d_babs = nullptr;
-  std::vector<void*> allocs;
+  DevPool allocs;           // what the setup allocated: the vectors above and the coefficients
   bool initialised = false;
   bool setup_done = false;
   int rk_order = 4;  // explicit Runge-Kutta scheme, tables of python/src/fenicsxfus/_linear.py:286-311
@@ -51,44 +183,10 @@ struct fus_model
   // k_boundary_partial only when they are not (first stage after init / set, other RK orders).
   bool bnd_valid = false;
   double bnd_tn = 0.0;
-  // receivers (fus_model_set_receivers): per point the internal indices of its cell's dofs and the 1-D basis
-  // values at its reference coordinates; record buffer for sampling every k steps inside the RK loops
-  int64_t rc_n = 0;
-  int32_t* d_rc_idx = nullptr;
-  void *d_rc_bas = nullptr, *d_rc_out = nullptr, *d_rec = nullptr;
-  int rec_every = 0, rec_which = 0;
-  int64_t rec_cap = 0, rec_n = 0, rec_step = 0;  // rec_cap: the records the last fus_model_record asked for
-  int64_t rec_alloc = 0;                         // records d_rec has room for (it only grows)
-  std::vector<double> rec_times;
-  // field monitor (fus_model_monitor): per-DOF accumulator planes over the internal vector, one allocation --
-  // T[2][n_internal] (max, min) then double[2 + 2 nharm][n_internal] (sum, sum of squares, cos_k, sin_k)
-  void* d_mon = nullptr;
-  size_t mon_bytes = 0;
-  int mon_every = 0, mon_which = 0, mon_nharm = 0;
-  double mon_freq = 0.0;
-  int64_t mon_skip = 0, mon_count = 0, mon_step = 0, mon_n = 0;
-  double mon_t_first = 0.0, mon_t_last = 0.0;
-  // phased / apodised source (fus_model_set_source).  src_mode 0: the default source, d_bsrc / d_bsrc2 hold the facet
-  // weights.  1: amplitude only -- the weights times the per-entry amplitude, folded in once; the scalar path stays.
-  // 2: delays or a burst -- k_source_entries writes d_bsrc / d_bsrc2 = weights x per-entry waveform for a stage time and
-  // the kernels get gval = dgval = 1.  d_src_base / d_src_base2 keep the unmodified weights, d_src_amp / d_src_tau the
-  // per-entry amplitude and delay, all in boundary-entry order.  src_tn_int / src_tn_sh: the stage time the block-interior
-  // entries [0, nb_int) and the shared entries [nb_int, nb) of d_bsrc hold (NaN: none).
-  // 3: sampled drive signals (fus_model_set_source_signals) -- as 2, with k_source_entries_signal: d_src_chan is the
-  // channel of every entry (-1: silent), renumbered in order of first use along the entry list, d_src_table the samples
-  // time-major, double[nsamp][src_sig.nchan].
-  int src_mode = 0;
-  void *d_src_base = nullptr, *d_src_base2 = nullptr, *d_src_amp = nullptr, *d_src_tau = nullptr;
-  int32_t* d_src_chan = nullptr;
-  double* d_src_table = nullptr;
-  fus::SourceSignal src_sig{};
-  double src_dur = 0.0;
-  double src_tn_int = NAN, src_tn_sh = NAN;
-  // The facet weights as the setup produced them, sparse, by ascending internal index (exact in double for both scalar
-  // types): what the entry lists are built from, at setup and again by fus_model_set_source_weights, whose weights
-  // only ever add to the src part.
-  std::vector<int32_t> h_fidx;
-  std::vector<double> h_fsrc, h_fabs, h_fsrc2;
+  ModelEntries bnd;
+  ModelSource src;
+  ModelReceivers rc;
+  ModelMonitor mon;
   // c0 and rho0 as fus_model_create was given them, internal cell order: fus_thermal_set_heat_from_monitor forms
   // q_coef = 2 alpha / (rho c) from them
   void *d_c0 = nullptr, *d_rho0 = nullptr;

@@ -11,6 +11,14 @@
 
 using namespace fus;
 
+// The boundary in force (fus_thermal_set_boundary; lists: thermal_bc.hpp): replaced as a whole
+struct FUS_HIDDEN ThermalBoundary
+{
+  int64_t nfix = 0, nconv = 0;
+  DevBuf fix_idx, conv_idx;          // int32
+  DevBuf fix_val, conv_hw, conv_r;   // T
+};
+
 // The operator action runs through d_apply_internal (STAGE_NONE block kernel + shared reduction) on the thermal object's
 // own vectors; of the op's scratch it takes d_partial (rewritten by every operator pass of any model; the wave models'
 // pseudo boundary slots behind n_partial are not touched), d_tmp_c and d_tmp_coef -- never d_tmp_x, whose padding
@@ -27,14 +35,11 @@ struct fus_thermal
   void *kneg = nullptr;        // -k per cell, internal cell order
   double* dose = nullptr;      // CEM43 minutes, n_internal doubles
   double* d_stage = nullptr;   // ndofs doubles in caller numbering (dose in / out)
-  // boundary conditions (fus_thermal_set_boundary; lists: thermal_bc.hpp).  minv_bc: the copy of minv with zeros at the
-  // fixed DOFs that the stage and power kernels read while nfix > 0, allocated by the first call that fixes a DOF
+  // minv_bc: the copy of minv with zeros at the fixed DOFs that the stage and power kernels read while bc.nfix > 0,
+  // allocated by the first call that fixes a DOF
   void* minv_bc = nullptr;
-  int64_t nfix = 0, nconv = 0;
-  int32_t *fix_idx = nullptr, *conv_idx = nullptr;
-  void *fix_val = nullptr, *conv_hw = nullptr, *conv_r = nullptr;
-  std::vector<void*> bc_allocs;   // the five lists of the boundary in force
-  std::vector<void*> allocs;
+  ThermalBoundary bc;
+  DevPool allocs;   // the vectors above, each allocated once
   bool initialised = false;
   // several ranks (fusmi.h "bioheat", several ranks): m_C, m_W, the heat weight and the fixed flags of the DOFs that other
   // ranks hold too are ordered sums over the sharers.  Under RCCL the call that forms them exchanges at once; in an
@@ -77,18 +82,19 @@ static int thermal_sum(fus_thermal** ths, int n, void* (*vec)(fus_thermal*))
 }
 
 // 1 / m_C as the stage and power kernels take it: zero at the fixed DOFs while there are any
-static const void* thermal_minv(const fus_thermal* th) { return th->nfix > 0 ? th->minv_bc : th->minv; }
+static const void* thermal_minv(const fus_thermal* th) { return th->bc.nfix > 0 ? th->minv_bc : th->minv; }
 
 // b += r - m_H x at the convective DOFs (r_too = false: the homogeneous part); nothing is enqueued without such DOFs
 template <typename T>
 static int thermal_robin(fus_thermal* th, const T* x, bool r_too)
 {
-  if (th->nconv == 0)
+  const ThermalBoundary& B = th->bc;
+  if (B.nconv == 0)
     return FUS_OK;
   ProfScope ps(th->ctx, "thermal_bc");
-  hipLaunchKernelGGL((k_thermal_robin<T>), dim3(nblk(th->nconv)), dim3(256), 0, th->ctx->stream, th->nconv,
-                     static_cast<const int32_t*>(th->conv_idx), static_cast<const T*>(th->conv_hw),
-                     r_too ? static_cast<const T*>(th->conv_r) : nullptr, x, static_cast<T*>(th->b));
+  hipLaunchKernelGGL((k_thermal_robin<T>), dim3(nblk(B.nconv)), dim3(256), 0, th->ctx->stream, B.nconv,
+                     B.conv_idx.as<const int32_t>(), B.conv_hw.as<const T>(), r_too ? B.conv_r.as<const T>() : nullptr, x,
+                     static_cast<T*>(th->b));
   HIPCHK(hipGetLastError());
   return FUS_OK;
 }
@@ -98,12 +104,13 @@ static int thermal_robin(fus_thermal* th, const T* x, bool r_too)
 template <typename T>
 static int thermal_impose(fus_thermal* th, void* vec, bool zero_values = false, bool with_minv = false)
 {
-  if (th->nfix == 0)
+  const ThermalBoundary& B = th->bc;
+  if (B.nfix == 0)
     return FUS_OK;
   ProfScope ps(th->ctx, "thermal_fix");
-  hipLaunchKernelGGL((k_thermal_fix<T>), dim3(nblk(th->nfix)), dim3(256), 0, th->ctx->stream, th->nfix,
-                     static_cast<const int32_t*>(th->fix_idx), zero_values ? nullptr : static_cast<const T*>(th->fix_val),
-                     static_cast<T*>(vec), with_minv ? static_cast<T*>(th->minv_bc) : nullptr);
+  hipLaunchKernelGGL((k_thermal_fix<T>), dim3(nblk(B.nfix)), dim3(256), 0, th->ctx->stream, B.nfix,
+                     B.fix_idx.as<const int32_t>(), zero_values ? nullptr : B.fix_val.as<const T>(), static_cast<T*>(vec),
+                     with_minv ? static_cast<T*>(th->minv_bc) : nullptr);
   HIPCHK(hipGetLastError());
   return FUS_OK;
 }
@@ -475,8 +482,8 @@ static int thermal_heat_from_monitor(fus_thermal* th, fus_model* m, const void* 
   hipLaunchKernelGGL((k_thermal_qcoef<T>), dim3(nblk(nc)), dim3(256), 0, st, nc, static_cast<const T*>(ci),
                      static_cast<const T*>(m->d_rho0), static_cast<const T*>(m->d_c0), cc);
   HIPCHK(hipGetLastError());
-  const double* Q = reinterpret_cast<const double*>(static_cast<const T*>(m->d_mon) + 2 * n) + n;   // acc plane 1
-  return thermal_heat<T>(th, cc, nullptr, Q, (double)m->mon_n);
+  const double* Q = reinterpret_cast<const double*>(m->mon.d_mon.as<const T>() + 2 * n) + n;   // acc plane 1
+  return thermal_heat<T>(th, cc, nullptr, Q, (double)m->mon.n);
 }
 
 // h = sum_k M(2 alpha_k / (rho c)) 1 .* (2 / n^2) (C_k^2 + S_k^2) over the harmonics 1..nharm of the model's monitor
@@ -502,8 +509,8 @@ static int thermal_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm,
   T* ci = cc + nc;
   T* mk = static_cast<T*>(th->b);
   T* out = static_cast<T*>(group ? th->mq : th->h);   // in a group h stays as it was until the finish
-  const double* acc = reinterpret_cast<const double*>(static_cast<const T*>(m->d_mon) + 2 * n);
-  const double ns = (double)m->mon_n;
+  const double* acc = reinterpret_cast<const double*>(m->mon.d_mon.as<const T>() + 2 * n);
+  const double ns = (double)m->mon.n;
   int64_t nvec;
   const unsigned grid = thermal_grid<T>(th, &nvec);
   for (int k = 1; k <= nharm; ++k)
@@ -516,7 +523,7 @@ static int thermal_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm,
     HIPCHK(hipGetLastError());
     FUSCHK(thermal_lumped<T>(th, cc, mk));
     hipLaunchKernelGGL((k_thermal_heat_harmonic<T>), dim3(grid), dim3(256), 0, st, nvec, static_cast<const T*>(mk),
-                       acc + (size_t)(1 + k) * n, acc + (size_t)(1 + m->mon_nharm + k) * n, static_cast<double*>(th->qp),
+                       acc + (size_t)(1 + k) * n, acc + (size_t)(1 + m->mon.nharm + k) * n, static_cast<double*>(th->qp),
                        k == 1 ? 1 : 0, k == nharm ? 2.0 / (ns * ns) : 0.0, out);
     HIPCHK(hipGetLastError());
   }
@@ -724,37 +731,25 @@ static int thermal_install_boundary(fus_thermal* th, const uint8_t* fixed, const
                                            static_cast<const T*>(conv_diag), static_cast<const T*>(conv_rise), &L);
   if (err != fus::TBC_OK)
     return fail(FUS_ERR_ARG, std::string("fus_thermal_set_boundary: ") + fus::thermal_bc_message(err));
-  std::vector<void*> fresh;
-  int32_t *fi = nullptr, *ci = nullptr;
-  T *fv = nullptr, *hw = nullptr, *r = nullptr;
-  int rc = FUS_OK;
-  if (!L.fix_idx.empty())
+  ThermalBoundary B;
+  const char* what = "boundary lists (fus_thermal_set_boundary)";
+  B.nfix = (int64_t)L.fix_idx.size(), B.nconv = (int64_t)L.conv_idx.size();
+  if (B.nfix > 0)
   {
-    rc = rc != FUS_OK ? rc : upload(fresh, &fi, L.fix_idx, st);
-    rc = rc != FUS_OK ? rc : upload(fresh, &fv, L.fix_val, st);
-    if (rc == FUS_OK && !th->minv_bc)
-      rc = dalloc_bytes(th->allocs, &th->minv_bc, n * sizeof(T), false, st);
+    FUSCHK(upload(B.fix_idx, L.fix_idx, st, what));
+    FUSCHK(upload(B.fix_val, L.fix_val, st, what));
+    if (!th->minv_bc)
+      FUSCHK(dalloc_bytes(th->allocs, &th->minv_bc, n * sizeof(T), false, st));
   }
-  if (!L.conv_idx.empty())
+  if (B.nconv > 0)
   {
-    rc = rc != FUS_OK ? rc : upload(fresh, &ci, L.conv_idx, st);
-    rc = rc != FUS_OK ? rc : upload(fresh, &hw, L.hw, st);
-    rc = rc != FUS_OK ? rc : upload(fresh, &r, L.r, st);
+    FUSCHK(upload(B.conv_idx, L.conv_idx, st, what));
+    FUSCHK(upload(B.conv_hw, L.hw, st, what));
+    FUSCHK(upload(B.conv_r, L.r, st, what));
   }
-  if (rc == FUS_OK && hipStreamSynchronize(st) != hipSuccess)   // the uploads read L
-    rc = fail(FUS_ERR_HIP, "fus_thermal_set_boundary: stream synchronisation failed");
-  if (rc != FUS_OK)
-  {
-    for (void* q : fresh)
-      (void)hipFree(q);
-    return rc;
-  }
-  for (void* q : th->bc_allocs)   // every step that read them has finished: the step calls synchronise
-    (void)hipFree(q);
-  th->bc_allocs = std::move(fresh);
-  th->nfix = (int64_t)L.fix_idx.size(), th->nconv = (int64_t)L.conv_idx.size();
-  th->fix_idx = fi, th->fix_val = fv, th->conv_idx = ci, th->conv_hw = hw, th->conv_r = r;
-  if (th->nfix > 0)
+  HIPCHK(hipStreamSynchronize(st));   // the uploads read L
+  th->bc = std::move(B);   // every step that read the previous lists has finished: the step calls synchronise
+  if (th->bc.nfix > 0)
   {
     HIPCHK(hipMemcpyAsync(th->minv_bc, th->minv, n * sizeof(T), hipMemcpyDeviceToDevice, st));
     // the rise of an object not yet initialised is rewritten by fus_thermal_init / fus_thermal_set, which impose again
@@ -936,11 +931,7 @@ int fus_thermal_create(fus_ctx* c, fus_op* op, const void* conductivity, const v
   th->ctx = c, th->op = op, th->t_base = t_base;
   const int r = FUS_BY_DTYPE(th->op->dtype, thermal_setup, th.get(), conductivity, rho_c, perfusion);
   if (r != FUS_OK)
-  {
-    for (void* q : th->allocs)
-      (void)hipFree(q);
-    return r;
-  }
+    return r;   // (th frees what the setup had allocated)
   *out = th.release();
   return FUS_OK;
 }
@@ -951,11 +942,7 @@ int fus_thermal_destroy(fus_thermal* th)
     return FUS_OK;
   (void)hipSetDevice(th->ctx->device);
   (void)hipStreamSynchronize(th->ctx->stream);
-  for (void* q : th->allocs)
-    (void)hipFree(q);
-  for (void* q : th->bc_allocs)
-    (void)hipFree(q);
-  delete th;
+  delete th;   // frees its arrays: nothing on the stream reads them any more
   return FUS_OK;
 }
 
@@ -1008,11 +995,11 @@ int fus_thermal_set_heat_from_monitor(fus_thermal* th, fus_model* m, const void*
     return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_monitor: null argument");
   if (m->op != th->op)
     return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_monitor: the model runs on another fus_op than the thermal object");
-  if (m->mon_every <= 0 || !m->d_mon)
+  if (m->mon.every <= 0 || !m->mon.d_mon)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the model's monitor is off (fus_model_monitor)");
-  if (m->mon_which != FUS_U)
+  if (m->mon.which != FUS_U)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the monitor watches FUS_V; the heat needs the pressure, FUS_U");
-  if (m->mon_n == 0)
+  if (m->mon.n == 0)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_monitor: the monitor has taken no sample yet");
   HIPCHK(hipSetDevice(th->ctx->device));
   return FUS_BY_DTYPE(th->op->dtype, thermal_heat_from_monitor, th, m, absorption);
@@ -1026,13 +1013,13 @@ int fus_thermal_set_heat_from_harmonics(fus_thermal* th, fus_model* m, int nharm
     return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: the model runs on another fus_op than the thermal object");
   if (nharm < 1 || nharm > 8)
     return fail(FUS_ERR_ARG, "fus_thermal_set_heat_from_harmonics: nharm must lie in 1..8");
-  if (m->mon_every <= 0 || !m->d_mon)
+  if (m->mon.every <= 0 || !m->mon.d_mon)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the model's monitor is off (fus_model_monitor)");
-  if (m->mon_which != FUS_U)
+  if (m->mon.which != FUS_U)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor watches FUS_V; the heat needs the pressure, FUS_U");
-  if (m->mon_n == 0)
+  if (m->mon.n == 0)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor has taken no sample yet");
-  if (nharm > m->mon_nharm)
+  if (nharm > m->mon.nharm)
     return fail(FUS_ERR_STATE, "fus_thermal_set_heat_from_harmonics: the monitor holds fewer harmonics than nharm asks for");
   HIPCHK(hipSetDevice(th->ctx->device));
   return FUS_BY_DTYPE(th->op->dtype, thermal_heat_from_harmonics, th, m, nharm, absorption);
@@ -1191,9 +1178,9 @@ int fus_thermal_boundary_info(fus_thermal* th, int64_t* nfixed, int64_t* nconvec
   if (!th)
     return fail(FUS_ERR_ARG, "fus_thermal_boundary_info: null argument");
   if (nfixed)
-    *nfixed = th->nfix;
+    *nfixed = th->bc.nfix;
   if (nconvective)
-    *nconvective = th->nconv;
+    *nconvective = th->bc.nconv;
   return FUS_OK;
 }
 

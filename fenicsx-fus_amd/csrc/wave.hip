@@ -214,24 +214,12 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
 // weights (parked in u_) and abs weights (parked in v_) of this rank's own facets
 static void* setup_halo_vector(fus_model* m, int k) { return k == 0 ? m->m : (k == 1 ? m->mn1 : m->v_); }
 
-// A device array of the model's pool: freed and taken off the pool (the entry lists are rebuilt)
-template <typename U>
-static void pool_release(std::vector<void*>& pool, U** p)
-{
-  if (!*p)
-    return;
-  auto it = std::find(pool.begin(), pool.end(), static_cast<void*>(*p));
-  if (it != pool.end())
-    pool.erase(it);
-  (void)hipFree(*p);
-  *p = nullptr;
-}
-
 // The boundary-entry lists: every internal dof with a non-zero source or absorbing weight, sorted by internal index --
 // bidx, nb, nb_int, d_blk_bnd_off, the pseudo pairs appended to d_sh_ptr32 / d_sh_pairs32, d_bnd_mask / d_bnd_base and
-// the weights d_bsrc, d_babs (and d_bsrc2).  Built from the facet weights the setup left (fus_model::h_f*) plus `vol`,
+// the weights d_bsrc, d_babs (and d_bsrc2).  Built from the facet weights the setup left (ModelSource::h_f*) plus `vol`,
 // the caller's source weights in internal numbering (n_internal long; nullptr: none), which add to the src part only.
-// Lists of an earlier call are freed.  The setup and fus_model_set_source_weights both end here.
+// The lists are built beside those in force and replace them at the end: an error leaves the model as it was.  The setup
+// and fus_model_set_source_weights both end here.
 template <typename T>
 static int model_build_entries(fus_model* m, const T* vol)
 {
@@ -245,7 +233,7 @@ static int model_build_entries(fus_model* m, const T* vol)
   std::vector<T> bsrc, babs, bsrc2;
   {
     size_t f = 0;
-    const size_t nf = m->h_fidx.size();
+    const size_t nf = m->src.h_fidx.size();
     auto entry = [&](int64_t i, T s, T a, T s2)
     {
       bidx.push_back((int32_t)i), bsrc.push_back(s), babs.push_back(a);
@@ -254,41 +242,38 @@ static int model_build_entries(fus_model* m, const T* vol)
     };
     if (!vol)
       for (; f < nf; ++f)
-        entry(m->h_fidx[f], (T)m->h_fsrc[f], (T)m->h_fabs[f], lossy ? (T)m->h_fsrc2[f] : T(0));
+        entry(m->src.h_fidx[f], (T)m->src.h_fsrc[f], (T)m->src.h_fabs[f], lossy ? (T)m->src.h_fsrc2[f] : T(0));
     else
       for (int64_t i = 0; i < n; ++i)
       {
-        const bool facet = f < nf && m->h_fidx[f] == i;
+        const bool facet = f < nf && m->src.h_fidx[f] == i;
         if (facet)
-          entry(i, (T)m->h_fsrc[f] + vol[i], (T)m->h_fabs[f], lossy ? (T)m->h_fsrc2[f] : T(0)), ++f;
+          entry(i, (T)m->src.h_fsrc[f] + vol[i], (T)m->src.h_fabs[f], lossy ? (T)m->src.h_fsrc2[f] : T(0)), ++f;
         else if (vol[i] != T(0))
           entry(i, vol[i], T(0), T(0));
       }
   }
-  for (int32_t** q : {&m->d_blk_bnd_off, &m->d_sh_ptr32, &m->d_sh_pairs32, &m->d_bnd_base, &m->d_bidx})
-    pool_release(m->allocs, q);
-  pool_release(m->allocs, &m->d_bnd_mask);
-  for (void** q : {&m->d_bsrc, &m->d_babs, &m->d_bsrc2})
-    pool_release(m->allocs, q);
-  m->nb = (int64_t)bidx.size();
+  ModelEntries F;
+  const char* what = "boundary-entry lists";
+  F.nb = (int64_t)bidx.size();
   {
-    m->nb_int = std::lower_bound(bidx.begin(), bidx.end(), (int32_t)L.n_int_pad) - bidx.begin();
+    F.nb_int = std::lower_bound(bidx.begin(), bidx.end(), (int32_t)L.n_int_pad) - bidx.begin();
     std::vector<int32_t> off(L.nblocks + 1);
     for (int32_t b = 0; b < L.nblocks; ++b)
-      off[b] = (int32_t)(std::lower_bound(bidx.begin(), bidx.begin() + m->nb_int, L.blk_int_off[b])
+      off[b] = (int32_t)(std::lower_bound(bidx.begin(), bidx.begin() + F.nb_int, L.blk_int_off[b])
                          - bidx.begin());
-    off[L.nblocks] = (int32_t)m->nb_int;
-    FUSCHK(upload(m->allocs, &m->d_blk_bnd_off, off, st));
+    off[L.nblocks] = (int32_t)F.nb_int;
+    FUSCHK(upload(F.d_blk_bnd_off, off, st, what));
     // shared CSR of this model: where the op's pairs keep their partial sums + one trailing pseudo pair (slot
     // n_partial + k) for the k-th shared boundary dof, so the boundary term is the last addend like
     // Linear.hpp:204-205
     if (L.n_partial + L.n_shared > 2000000000ll)
       return fail(FUS_ERR_LIMIT, "partial slab exceeds int32 indexing");
     std::vector<int32_t> extra(L.n_shared, -1);
-    for (int64_t k = m->nb_int; k < m->nb; ++k)
-      extra[bidx[k] - L.n_int_pad] = (int32_t)(L.n_partial + (k - m->nb_int));
+    for (int64_t k = F.nb_int; k < F.nb; ++k)
+      extra[bidx[k] - L.n_int_pad] = (int32_t)(L.n_partial + (k - F.nb_int));
     std::vector<int32_t> ptr(L.n_shared + 1), prs;
-    prs.reserve(L.npairs + (m->nb - m->nb_int));
+    prs.reserve(L.npairs + (F.nb - F.nb_int));
     for (int64_t sidx = 0; sidx < L.n_shared; ++sidx)
     {
       ptr[sidx] = (int32_t)prs.size();
@@ -298,12 +283,11 @@ static int model_build_entries(fus_model* m, const T* vol)
         prs.push_back(extra[sidx]);
     }
     ptr[L.n_shared] = (int32_t)prs.size();
-    FUSCHK(upload(m->allocs, &m->d_sh_ptr32, ptr, st));
-    FUSCHK(upload(m->allocs, &m->d_sh_pairs32, prs, st));
+    FUSCHK(upload(F.d_sh_ptr32, ptr, st, what));
+    FUSCHK(upload(F.d_sh_pairs32, prs, st, what));
     // the same for the plane form of the rank-local shared dofs (k_shared_stage_planes): one bit per dof and the
     // number of boundary dofs ahead of each 64-dof word (bidx ascends, so the k-th set bit is the k-th term)
-    m->d_bnd_mask = nullptr, m->d_bnd_base = nullptr;
-    if (m->nb > m->nb_int && L.n_shared_local > 0)
+    if (F.nb > F.nb_int && L.n_shared_local > 0)
     {
       const int64_t nw = (L.n_shared_local + 63) / 64;
       std::vector<uint64_t> mask(nw, 0);
@@ -314,22 +298,17 @@ static int model_build_entries(fus_model* m, const T* vol)
       // boundary dofs of the interface range come after every local one in bidx, so the local ranks start at 0
       for (int64_t w = 1; w < nw; ++w)
         base[w] = base[w - 1] + __builtin_popcountll(mask[w - 1]);
-      FUSCHK(upload(m->allocs, &m->d_bnd_mask, mask, st));
-      FUSCHK(upload(m->allocs, &m->d_bnd_base, base, st));
+      FUSCHK(upload(F.d_bnd_mask, mask, st, what));
+      FUSCHK(upload(F.d_bnd_base, base, st, what));
     }
   }
-  T *d_bsrc, *d_babs;
-  FUSCHK(upload(m->allocs, &m->d_bidx, bidx, st));
-  FUSCHK(upload(m->allocs, &d_bsrc, bsrc, st));
-  FUSCHK(upload(m->allocs, &d_babs, babs, st));
-  m->d_bsrc = d_bsrc, m->d_babs = d_babs;
+  FUSCHK(upload(F.d_bidx, bidx, st, what));
+  FUSCHK(upload(F.d_bsrc, bsrc, st, what));
+  FUSCHK(upload(F.d_babs, babs, st, what));
   if (lossy)
-  {
-    T* d_bsrc2;
-    FUSCHK(upload(m->allocs, &d_bsrc2, bsrc2, st));
-    m->d_bsrc2 = d_bsrc2;
-  }
-  HIPCHK(hipStreamSynchronize(st));   // the host vectors leave scope
+    FUSCHK(upload(F.d_bsrc2, bsrc2, st, what));
+  HIPCHK(hipStreamSynchronize(st));   // the host vectors leave scope; no kernel reads the previous lists (synchronised above)
+  m->bnd = std::move(F);
   return FUS_OK;
 }
 
@@ -348,15 +327,15 @@ static int model_setup_finish(fus_model* m)
   if (lossy)
     HIPCHK(hipMemcpyAsync(src2.data(), m->vn, n * sizeof(T), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  m->h_fidx.clear(), m->h_fsrc.clear(), m->h_fabs.clear(), m->h_fsrc2.clear();
+  m->src.h_fidx.clear(), m->src.h_fsrc.clear(), m->src.h_fabs.clear(), m->src.h_fsrc2.clear();
   for (int64_t i = 0; i < n; ++i)
     if (src[i] != T(0) || absb[i] != T(0) || (lossy && src2[i] != T(0)))
     {
-      m->h_fidx.push_back((int32_t)i);
-      m->h_fsrc.push_back((double)src[i]);
-      m->h_fabs.push_back((double)absb[i]);
+      m->src.h_fidx.push_back((int32_t)i);
+      m->src.h_fsrc.push_back((double)src[i]);
+      m->src.h_fabs.push_back((double)absb[i]);
       if (lossy)
-        m->h_fsrc2.push_back((double)src2[i]);
+        m->src.h_fsrc2.push_back((double)src2[i]);
     }
   FUSCHK(model_build_entries<T>(m, nullptr));
   HIPCHK(hipMemsetAsync(m->u_, 0, n * sizeof(T), st));
@@ -482,46 +461,45 @@ static StageArgs<T> stage_args(fus_model* m, int i, const StageScalars& sc)
   S.u_ = V.u_, S.v_ = V.v_;
   S.adt = (T)sc.adt, S.bdt = (T)sc.bdt, S.gval = (T)sc.gval;
   S.b0dt = (T)sc.b0dt, S.pdt = (T)sc.pdt, S.third = T(1) / T(3);
-  S.blk_bnd_off = m->d_blk_bnd_off, S.bnd_idx = m->d_bidx;
-  S.bnd_src = static_cast<const T*>(m->d_bsrc), S.bnd_abs = static_cast<const T*>(m->d_babs);
+  S.blk_bnd_off = m->bnd.d_blk_bnd_off.as<int32_t>(), S.bnd_idx = m->bnd.d_bidx.as<int32_t>();
+  S.bnd_src = m->bnd.d_bsrc.as<const T>(), S.bnd_abs = m->bnd.d_babs.as<const T>();
   S.x2 = nullptr, S.coef2 = static_cast<const T*>(m->coef2);
-  S.bnd_src2 = static_cast<const T*>(m->d_bsrc2), S.dgval = (T)sc.dgval;
+  S.bnd_src2 = m->bnd.d_bsrc2.as<const T>(), S.dgval = (T)sc.dgval;
   S.m0 = static_cast<const T*>(m->m), S.mn1 = static_cast<const T*>(m->mn1);
   return S;
 }
 
-// Per-entry source (src_mode 2, and 3 with the sampled signals): the weight arrays of the entries [k0, k1) for the stage time tn.  The rule of the
-// callers: before a kernel reads a range of d_bsrc / d_bsrc2, the range holds the values for the time whose scalar
-// that kernel would have carried -- the block kernel and k_boundary_partial the stage's own time, the shared-dof and
-// interface stage kernels (BndNext) the next stage's.
+// Per-entry source (src.mode 2, and 3 with the sampled signals): the weight arrays of the entries [k0, k1) for the stage
+// time tn.  The rule of the callers: before a kernel reads a range of d_bsrc / d_bsrc2, the range holds the values for the
+// time whose scalar that kernel would have carried -- the block kernel and k_boundary_partial the stage's own time, the
+// shared-dof and interface stage kernels (BndNext) the next stage's.
 template <typename T>
 static int source_entries(fus_model* m, int64_t k0, int64_t k1, double tn)
 {
   if (k1 <= k0)
     return FUS_OK;
   const bool lossy = m->kind == FUS_LOSSY || m->kind == FUS_WESTERVELT;
-  if (m->src_mode == 3)
+  const ModelSource::Arrays& A = m->src.d;
+  T *out = m->bnd.d_bsrc.as<T>(), *out2 = m->bnd.d_bsrc2.as<T>();
+  if (m->src.mode == 3)
   {
     ProfScope ps(m->ctx, "source_signal");
     hipLaunchKernelGGL((k_source_entries_signal<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
-                       static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
-                       static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), m->d_src_chan,
-                       m->d_src_table, m->src_sig, tn, static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+                       A.base.as<const T>(), A.base2.as<const T>(), A.amp.as<const T>(), A.tau.as<const T>(),
+                       A.chan.as<int32_t>(), A.table.as<double>(), m->src.sig, tn, out, out2);
   }
   else
   {
-    const SourceWave W = source_wave_make(m->freq, m->amp, m->speed, (lossy && m->forms == 0) ? 2.0 : 1.0, m->src_dur);
+    const SourceWave W = source_wave_make(m->freq, m->amp, m->speed, (lossy && m->forms == 0) ? 2.0 : 1.0, m->src.dur);
     ProfScope ps(m->ctx, "source");
     hipLaunchKernelGGL((k_source_entries<T>), dim3(nblk(k1 - k0)), dim3(256), 0, m->ctx->stream, k0, k1,
-                       static_cast<const T*>(m->d_src_base), static_cast<const T*>(m->d_src_base2),
-                       static_cast<const T*>(m->d_src_amp), static_cast<const T*>(m->d_src_tau), W, tn,
-                       static_cast<T*>(m->d_bsrc), static_cast<T*>(m->d_bsrc2));
+                       A.base.as<const T>(), A.base2.as<const T>(), A.amp.as<const T>(), A.tau.as<const T>(), W, tn, out, out2);
   }
   HIPCHK(hipGetLastError());
   if (k0 == 0)
-    m->src_tn_int = tn;
-  if (k1 == m->nb)
-    m->src_tn_sh = tn;
+    m->src.tn_int = tn;
+  if (k1 == m->bnd.nb)
+    m->src.tn_sh = tn;
   return FUS_OK;
 }
 
@@ -550,16 +528,16 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   // launch costs more (2.47 vs 2.41 ms per step at 64^3 p=4) than it hides.  A block's epilogue only writes that block's interior dofs,
   // which no other block and none of the small kernels below reads.
   // boundary terms of the shared boundary dofs: a launch of their own unless the previous stage left them (below)
-  const int64_t nbs = m->nb - m->nb_int;
+  const int64_t nbs = m->bnd.nb - m->bnd.nb_int;
   const bool bnd_launch = nbs > 0 && !(m->bnd_valid && op->bnd_owner == m && m->bnd_tn == sc_now.tn);
-  if (m->src_mode >= 2)   // 2: the analytic waveform per entry, 3: sampled signals
+  if (m->src.mode >= 2)   // 2: the analytic waveform per entry, 3: sampled signals
   {
     // the source rides in the weights: the block-interior entries for this stage's time, the shared ones too when
     // k_boundary_partial reads them; in the steady RK4 state the previous stage_end has left both
     S.gval = T(1), S.dgval = T(1);
-    const bool need_int = !(m->src_tn_int == sc_now.tn), need_sh = bnd_launch && !(m->src_tn_sh == sc_now.tn);
+    const bool need_int = !(m->src.tn_int == sc_now.tn), need_sh = bnd_launch && !(m->src.tn_sh == sc_now.tn);
     if (need_int || need_sh)
-      FUSCHK(source_entries<T>(m, need_int ? 0 : m->nb_int, need_sh ? m->nb : m->nb_int, sc_now.tn));
+      FUSCHK(source_entries<T>(m, need_int ? 0 : m->bnd.nb_int, need_sh ? m->bnd.nb : m->bnd.nb_int, sc_now.tn));
   }
   const int nb_if = op->L.nblocks_if;
   const bool split = m->ctx->overlap_blocks && !op->neigh.empty() && nb_if > 0 && nb_if < op->L.nblocks;
@@ -573,10 +551,9 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   {
     ProfScope ps(m->ctx, "boundary");
     hipLaunchKernelGGL((k_boundary_partial<T>), dim3(nblk(nbs)), dim3(256), 0, st, nbs,
-                       m->d_bidx + m->nb_int, static_cast<const T*>(m->d_bsrc) + m->nb_int,
-                       static_cast<const T*>(m->d_babs) + m->nb_int, S.gval,
-                       m->d_bsrc2 ? static_cast<const T*>(m->d_bsrc2) + m->nb_int : nullptr, S.dgval,
-                       vstage, static_cast<T*>(op->d_partial) + op->L.n_partial);
+                       S.bnd_idx + m->bnd.nb_int, S.bnd_src + m->bnd.nb_int, S.bnd_abs + m->bnd.nb_int, S.gval,
+                       S.bnd_src2 ? S.bnd_src2 + m->bnd.nb_int : nullptr, S.dgval, vstage,
+                       static_cast<T*>(op->d_partial) + op->L.n_partial);
   }
   // interface dofs (held by other ranks too): this rank's partials are summed into b and into the
   // send buffer by one kernel; the event hands the buffer to the exchange
@@ -584,7 +561,7 @@ static int stage_begin(fus_model* m, int i, double t, double dt)
   {
     ProfScope ps(m->ctx, "halo");
     hipLaunchKernelGGL((k_if_reduce_pack<T>), dim3(nblk(op->n_halo)), dim3(256), 0, st, op->n_halo,
-                       op->d_pack_idx, op->L.n_int_pad, m->d_sh_ptr32, m->d_sh_pairs32,
+                       op->d_pack_idx, op->L.n_int_pad, m->bnd.d_sh_ptr32.as<int32_t>(), m->bnd.d_sh_pairs32.as<int32_t>(),
                        static_cast<const T*>(op->d_partial), b, static_cast<T*>(op->d_sendbuf));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->ctx->ev_packed, st));
@@ -615,6 +592,7 @@ static int stage_end(fus_model* m, int i, double t, double dt)
   const T* minv = static_cast<const T*>(m->minv);
   const T* partial = static_cast<const T*>(op->d_partial);
   const int64_t off = op->L.n_int_pad, nloc = op->L.n_shared_local;
+  const int32_t *sh_ptr32 = m->bnd.d_sh_ptr32.as<int32_t>(), *sh_pairs32 = m->bnd.d_sh_pairs32.as<int32_t>();
   // Westervelt: m0 and mn1 on the shared range (nullptr otherwise)
   const T* m0p = m->mn1 ? static_cast<const T*>(m->m) + off : nullptr;
   const T* mn1p = m->mn1 ? static_cast<const T*>(m->mn1) + off : nullptr;
@@ -622,28 +600,28 @@ static int stage_end(fus_model* m, int i, double t, double dt)
   // in their pseudo partial slots (next stage of this step, or stage 0 of the next step at t + dt,
   // advanced the way the step loops do: in T for fus_model_rk4, whose t is a T)
   BndNext<T> B{};
-  const int64_t nbs = m->nb - m->nb_int;
+  const int64_t nbs = m->bnd.nb - m->bnd.nb_int;
   m->bnd_valid = false;
   if (m->rk_order == 4 && nbs > 0 && op->L.n_partial + nbs < INT32_MAX)
   {
     const StageScalars scn = i < 3 ? stage_scalars<T>(m, i + 1, t, dt)
                                    : stage_scalars<T>(m, 0, (double)((T)t + (T)dt), dt);
     B.enabled = 1, B.npairs = (int32_t)op->L.n_partial;
-    B.srcw = static_cast<const T*>(m->d_bsrc) + m->nb_int;
-    B.absw = static_cast<const T*>(m->d_babs) + m->nb_int;
-    B.src2w = m->d_bsrc2 ? static_cast<const T*>(m->d_bsrc2) + m->nb_int : nullptr;
+    B.srcw = m->bnd.d_bsrc.as<const T>() + m->bnd.nb_int;
+    B.absw = m->bnd.d_babs.as<const T>() + m->bnd.nb_int;
+    B.src2w = m->bnd.d_bsrc2 ? m->bnd.d_bsrc2.as<const T>() + m->bnd.nb_int : nullptr;
     B.gnext = (T)scn.gval, B.dgnext = (T)scn.dgval;
     B.partial = static_cast<T*>(op->d_partial);
     m->bnd_valid = true, m->bnd_tn = scn.tn;
     op->bnd_owner = m;
-    if (m->src_mode >= 2)
+    if (m->src.mode >= 2)
     {
       // the kernels below read the shared entries for the next stage's time; the same launch leaves the
       // block-interior entries for the next stage's block kernel (this stage's has run: same stream)
       B.gnext = T(1), B.dgnext = T(1);
-      const bool need_int = !(m->src_tn_int == scn.tn);
-      if (need_int || !(m->src_tn_sh == scn.tn))
-        FUSCHK(source_entries<T>(m, need_int ? 0 : m->nb_int, m->nb, scn.tn));
+      const bool need_int = !(m->src.tn_int == scn.tn);
+      if (need_int || !(m->src.tn_sh == scn.tn))
+        FUSCHK(source_entries<T>(m, need_int ? 0 : m->bnd.nb_int, m->bnd.nb, scn.tn));
     }
   }
   const LeanRK<T> R{(T)sc.b0dt, (T)sc.pdt, T(1) / T(3)};
@@ -659,7 +637,8 @@ static int stage_end(fus_model* m, int i, double t, double dt)
       PL.cnt[j] = (int32_t)op->L.plane_cnt[j], PL.off[j] = (int32_t)op->L.plane_off[j];
     FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      hipLaunchKernelGGL((k_shared_stage_planes<T, decltype(K)::value>), grid, blk, 0, st, nloc, PL, m->d_bnd_mask, m->d_bnd_base,
+      hipLaunchKernelGGL((k_shared_stage_planes<T, decltype(K)::value>), grid, blk, 0, st, nloc, PL,
+                         m->bnd.d_bnd_mask.as<uint64_t>(), m->bnd.d_bnd_base.as<int32_t>(),
                          partial, minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt,
                          m0p, mn1p, B, R);
       return FUS_OK;
@@ -671,7 +650,7 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     const dim3 grid(nblk(nloc)), blk(256);
     FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
-      hipLaunchKernelGGL((k_shared_stage<T, decltype(K)::value>), grid, blk, 0, st, nloc, m->d_sh_ptr32, m->d_sh_pairs32, partial,
+      hipLaunchKernelGGL((k_shared_stage<T, decltype(K)::value>), grid, blk, 0, st, nloc, sh_ptr32, sh_pairs32, partial,
                          minv + off, vn + off, un + off, u0 + off, v0 + off, u_ + off, v_ + off, adt, bdt, m0p, mn1p, B,
                          R);
       return FUS_OK;
@@ -691,8 +670,7 @@ static int stage_end(fus_model* m, int i, double t, double dt)
     FUSCHK(with_kind<FUS_STAGE_KINDS>(kind, [&](auto K) -> int
     {
       hipLaunchKernelGGL((k_if_unpack_stage<T, decltype(K)::value>), grid, blk, 0, st, op->n_uidx, op->d_uidx, op->d_uptr, op->d_usrc,
-                         recv, b, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0f, mn1f, op->L.n_int_pad, m->d_sh_ptr32,
-                         m->d_sh_pairs32, B, R);
+                         recv, b, minv, vn, un, u0, v0, u_, v_, adt, bdt, m0f, mn1f, op->L.n_int_pad, sh_ptr32, sh_pairs32, B, R);
       return FUS_OK;
     }));
   }
@@ -734,7 +712,7 @@ static int model_getset(fus_model* m, void* vec_, void* host_or_dev, int space, 
 
 // ---- field monitor: typed launches (the C entry points are fus_model_monitor* below) ----
 template <typename T, int NH>
-static void launch_monitor(fus_model* m, const double* c, const double* s)
+static int launch_monitor(fus_model* m, const double* c, const double* s)
 {
   const int64_t n = m->op->L.n_internal;
   const int64_t nvec = n / (16 / (int64_t)sizeof(T));
@@ -742,27 +720,17 @@ static void launch_monitor(fus_model* m, const double* c, const double* s)
   for (int k = 0; k < NH; ++k)
     ph.c[k] = c[k], ph.s[k] = s[k];
   const unsigned grid = (unsigned)std::min<int64_t>((nvec + 255) / 256, (int64_t)m->ctx->num_cus * 8);
-  T* ext = static_cast<T*>(m->d_mon);
+  T* ext = m->mon.d_mon.as<T>();
   double* acc = reinterpret_cast<double*>(ext + 2 * n);
   hipLaunchKernelGGL((k_monitor_accumulate<T, NH>), dim3(grid), dim3(256), 0, m->ctx->stream, nvec, n,
-                     m->mon_n == 0 ? 1 : 0, static_cast<const T*>(m->mon_which == FUS_U ? m->u0 : m->v0), ext, acc, ph);
+                     m->mon.n == 0 ? 1 : 0, static_cast<const T*>(m->mon.which == FUS_U ? m->u0 : m->v0), ext, acc, ph);
+  return FUS_OK;
 }
 
 template <typename T>
-static void launch_monitor_nh(fus_model* m, const double* c, const double* s)
+static int launch_monitor_nh(fus_model* m, const double* c, const double* s)
 {
-  switch (m->mon_nharm)
-  {
-  case 0: launch_monitor<T, 0>(m, c, s); break;
-  case 1: launch_monitor<T, 1>(m, c, s); break;
-  case 2: launch_monitor<T, 2>(m, c, s); break;
-  case 3: launch_monitor<T, 3>(m, c, s); break;
-  case 4: launch_monitor<T, 4>(m, c, s); break;
-  case 5: launch_monitor<T, 5>(m, c, s); break;
-  case 6: launch_monitor<T, 6>(m, c, s); break;
-  case 7: launch_monitor<T, 7>(m, c, s); break;
-  default: launch_monitor<T, 8>(m, c, s); break;
-  }
+  return with_kind<0, 1, 2, 3, 4, 5, 6, 7, 8>(m->mon.nharm, [&](auto NH) { return launch_monitor<T, decltype(NH)::value>(m, c, s); });
 }
 
 template <typename T>
@@ -771,7 +739,7 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
   fus_op* op = m->op;
   hipStream_t st = m->ctx->stream;
   const int64_t n = op->L.n_internal;
-  const T* ext = static_cast<const T*>(m->d_mon);
+  const T* ext = m->mon.d_mon.as<const T>();
   const double* acc = reinterpret_cast<const double*>(ext + 2 * n);
   const T* src = nullptr;
   if (quantity == FUS_MON_MAX || quantity == FUS_MON_MIN)
@@ -779,12 +747,12 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
   else
   {
     const int plane = quantity == FUS_MON_MEAN ? 0 : quantity == FUS_MON_RMS ? 1
-                      : quantity == FUS_MON_COS ? 1 + k : 1 + m->mon_nharm + k;
+                      : quantity == FUS_MON_COS ? 1 + k : 1 + m->mon.nharm + k;
     const double num = (quantity == FUS_MON_COS || quantity == FUS_MON_SIN) ? 2.0 : 1.0;
     T* fin = static_cast<T*>(op->d_tmp_x);
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)m->ctx->num_cus * 8);
     hipLaunchKernelGGL((k_monitor_finalise<T>), dim3(grid), dim3(256), 0, st, n, acc + (size_t)plane * n, num,
-                       (double)m->mon_n, quantity == FUS_MON_RMS ? 1 : 0, fin);
+                       (double)m->mon.n, quantity == FUS_MON_RMS ? 1 : 0, fin);
     src = fin;
   }
   T* tc = static_cast<T*>(op->d_tmp_c);
@@ -799,143 +767,157 @@ static int monitor_get(fus_model* m, int quantity, int k, void* out, int space)
   return FUS_OK;
 }
 
-// ---- phased / apodised source (fusmi.h) ----
-// the channel list and the sample table of the sampled signals
-static void signal_free(fus_model* m)
+// "The next step must not trust what the last one left", by what changed; each level includes those before it.
+// CHANGED_ORDER: the pseudo boundary partials were left for a stage time of the old scheme.  CHANGED_STATE: they carry the
+// old state, and the next step runs directly, not as a graph replay.  CHANGED_SOURCE: they carry the old source, and the
+// per-entry weights in d_bsrc / d_bsrc2 hold no stage time any more.
+enum { CHANGED_ORDER, CHANGED_STATE, CHANGED_SOURCE };
+static void model_changed(fus_model* m, int what)
 {
-  if (m->d_src_chan)
-    (void)hipFree(m->d_src_chan);
-  if (m->d_src_table)
-    (void)hipFree(m->d_src_table);
-  m->d_src_chan = nullptr, m->d_src_table = nullptr;
+  m->bnd_valid = false;
+  if (what >= CHANGED_STATE)
+    m->gsteps = 0;
+  if (what >= CHANGED_SOURCE)
+    m->src.tn_int = m->src.tn_sh = NAN;
 }
 
-static void source_free(fus_model* m)
+// ---- phased / apodised source (fusmi.h) ----
+// (not a hot path: every copy on the model's stream, complete on return)
+static int copy_sync(hipStream_t st, void* dst, const void* src, size_t nbytes, hipMemcpyKind kind)
 {
-  for (void** q : {&m->d_src_base, &m->d_src_base2, &m->d_src_amp, &m->d_src_tau})
+  if (nbytes > 0)
+    HIPCHK(hipMemcpyAsync(dst, src, nbytes, kind, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FUS_OK;
+}
+
+// A caller vector of ndofs T as a host pointer: v itself, or its copy in buf when it lives on the device (NULL stays NULL)
+template <typename T>
+static int caller_on_host(fus_model* m, const void* v, int space, std::vector<T>& buf, const T** out)
+{
+  *out = static_cast<const T*>(v);
+  if (!v || space != FUS_DEVICE)
+    return FUS_OK;
+  buf.resize(m->op->ndofs);
+  *out = buf.data();
+  return copy_sync(m->ctx->stream, buf.data(), v, buf.size() * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+// What the two per-entry setters (fn: the one that was called) start from, in boundary-entry order: the source weights
+// base / base2 as the setup (or fus_model_set_source_weights) left them, and for the entries that carry one the caller's
+// dof with the validated amplitude and delay (dof -1, amplitude and delay 0 at the others: pure absorbing entries).
+// keep / keep2: device copies of base / base2 for ModelSource::Arrays when the model does not keep them yet.
+template <typename T>
+struct FUS_HIDDEN SourcePrep
+{
+  std::vector<int32_t> dof;
+  std::vector<T> base, base2, amp, tau;
+  DevBuf keep, keep2;
+};
+
+// Fills P and changes nothing of the model.
+template <typename T>
+static int source_prepare(fus_model* m, const char* fn, const void* amplitude, const void* delay, int space, SourcePrep<T>* P)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const ModelEntries& B = m->bnd;
+  const ModelSource::Arrays& D = m->src.d;
+  const int64_t nb = B.nb;
+  std::vector<int32_t> bidx(nb);
+  P->base.resize(nb), P->base2.resize(B.d_bsrc2 ? nb : 0);
+  FUSCHK(copy_sync(st, bidx.data(), B.d_bidx.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+  FUSCHK(copy_sync(st, P->base.data(), (D.base ? D.base : B.d_bsrc).p, (size_t)nb * sizeof(T), hipMemcpyDeviceToHost));
+  FUSCHK(copy_sync(st, P->base2.data(), (D.base2 ? D.base2 : B.d_bsrc2).p, P->base2.size() * sizeof(T), hipMemcpyDeviceToHost));
+  std::vector<T> hbuf[2];
+  const T* h[2];
+  FUSCHK(caller_on_host(m, amplitude, space, hbuf[0], &h[0]));
+  FUSCHK(caller_on_host(m, delay, space, hbuf[1], &h[1]));
+  // gather through dof_perm into boundary-entry order; only the entries with a source weight count
+  std::vector<int32_t> caller(op->L.n_internal, -1);
+  for (int64_t d = 0; d < op->ndofs; ++d)
+    caller[op->L.dof_perm[d]] = (int32_t)d;
+  P->dof.assign(nb, -1), P->amp.assign(nb, T(0)), P->tau.assign(nb, T(0));
+  for (int64_t k = 0; k < nb; ++k)
   {
-    if (*q)
-      (void)hipFree(*q);
-    *q = nullptr;
+    if (P->base[k] == T(0) && (P->base2.empty() || P->base2[k] == T(0)))
+      continue;
+    const int32_t d = caller[bidx[k]];
+    const T a = h[0] ? h[0][d] : T(1), td = h[1] ? h[1][d] : T(0);
+    if (!std::isfinite((double)a) || a < T(0) || !std::isfinite((double)td) || td < T(0))
+      return fail(FUS_ERR_ARG, std::string(fn) + ": negative or non-finite amplitude / delay at dof " + std::to_string(d)
+                                   + " of the source");
+    P->dof[k] = d, P->amp[k] = a, P->tau[k] = td;
   }
-  signal_free(m);
+  if (!D.base)
+  {
+    FUSCHK(upload(P->keep, P->base, st, "source weights"));
+    if (B.d_bsrc2)
+      FUSCHK(upload(P->keep2, P->base2, st, "source weights"));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return FUS_OK;
+}
+
+// The per-entry arrays A go in force (moves: nothing can fail); the unmodified weights stay the ones the model keeps
+// already, or become P's copies.  Whatever A leaves empty is freed: the sampled signals, if a call without them was made
+template <typename T>
+static void source_install(fus_model* m, ModelSource::Arrays& A, SourcePrep<T>& P)
+{
+  ModelSource::Arrays& D = m->src.d;
+  if (!D.base)
+    D.base = std::move(P.keep), D.base2 = std::move(P.keep2);
+  A.base = std::move(D.base), A.base2 = std::move(D.base2);
+  D = std::move(A);
 }
 
 template <typename T>
 static int model_set_source(fus_model* m, const void* amplitude, const void* delay, double duration, int space)
 {
-  fus_op* op = m->op;
   hipStream_t st = m->ctx->stream;
-  const int64_t nb = m->nb;
-  const size_t bytes = (size_t)nb * sizeof(T);
+  ModelEntries& B = m->bnd;
+  ModelSource& S = m->src;
+  const size_t bytes = (size_t)B.nb * sizeof(T), bytes2 = B.d_bsrc2 ? bytes : 0;
   HIPCHK(hipStreamSynchronize(st));
-  // (not a hot path: every copy on the model's stream, complete on return)
-  auto copy = [&](void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) -> int
-  {
-    HIPCHK(hipMemcpyAsync(dst, src, nbytes, kind, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return FUS_OK;
-  };
-  auto changed = [&]()
-  {
-    m->bnd_valid = false;   // the pseudo boundary partials carry the old source
-    m->gsteps = 0;          // the next step runs directly, as after fus_model_set
-    m->src_tn_int = m->src_tn_sh = NAN;
-  };
   if (!amplitude && !delay && duration == 0.0)
   {
     // the default source: the facet weights go back where the kernels read them
-    if (m->d_src_base)
+    if (S.d.base)
     {
-      if (nb > 0)
-        FUSCHK(copy(m->d_bsrc, m->d_src_base, bytes, hipMemcpyDeviceToDevice));
-      if (nb > 0 && m->d_bsrc2)
-        FUSCHK(copy(m->d_bsrc2, m->d_src_base2, bytes, hipMemcpyDeviceToDevice));
-      source_free(m);
+      FUSCHK(copy_sync(st, B.d_bsrc.p, S.d.base.p, bytes, hipMemcpyDeviceToDevice));
+      FUSCHK(copy_sync(st, B.d_bsrc2.p, S.d.base2.p, bytes2, hipMemcpyDeviceToDevice));
+      S.d = {};
     }
-    m->src_mode = 0, m->src_dur = 0.0;
-    changed();
+    S.mode = 0, S.dur = 0.0;
+    model_changed(m, CHANGED_SOURCE);
     return FUS_OK;
   }
   if (!source_duration_ok(m->freq, duration))
     return fail(FUS_ERR_ARG, "fus_model_set_source: duration is 0 (continuous) or at least two ramp lengths, 8 / freq");
-  // the facet weights and the entries' internal indices, as the setup left them
-  std::vector<int32_t> bidx(nb);
-  std::vector<T> base(nb), base2(m->d_bsrc2 ? nb : 0);
-  if (nb > 0)
+  SourcePrep<T> P;
+  FUSCHK(source_prepare<T>(m, "fus_model_set_source", amplitude, delay, space, &P));
+  const bool fold = !delay && duration == 0.0;   // amplitude only: folded into the weights once, the scalar path stays
+  ModelSource::Arrays A;
+  if (!fold)
   {
-    FUSCHK(copy(bidx.data(), m->d_bidx, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
-    FUSCHK(copy(base.data(), m->d_src_base ? m->d_src_base : m->d_bsrc, bytes, hipMemcpyDeviceToHost));
-    if (m->d_bsrc2)
-      FUSCHK(copy(base2.data(), m->d_src_base2 ? m->d_src_base2 : m->d_bsrc2, bytes, hipMemcpyDeviceToHost));
-  }
-  // caller vectors on the host
-  std::vector<T> hbuf[2];
-  const T* h[2] = {static_cast<const T*>(amplitude), static_cast<const T*>(delay)};
-  for (int j = 0; j < 2; ++j)
-    if (h[j] && space == FUS_DEVICE)
-    {
-      hbuf[j].resize(op->ndofs);
-      FUSCHK(copy(hbuf[j].data(), h[j], (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost));
-      h[j] = hbuf[j].data();
-    }
-  // gather through dof_perm into boundary-entry order; only the entries with a source weight count
-  std::vector<int32_t> caller(op->L.n_internal, -1);
-  for (int64_t d = 0; d < op->ndofs; ++d)
-    caller[op->L.dof_perm[d]] = (int32_t)d;
-  std::vector<T> amp(nb, T(0)), tau(nb, T(0));
-  for (int64_t k = 0; k < nb; ++k)
-  {
-    if (base[k] == T(0) && (base2.empty() || base2[k] == T(0)))
-      continue;
-    const int32_t d = caller[bidx[k]];
-    const T a = h[0] ? h[0][d] : T(1), td = h[1] ? h[1][d] : T(0);
-    if (!std::isfinite((double)a) || a < T(0) || !std::isfinite((double)td) || td < T(0))
-      return fail(FUS_ERR_ARG, "fus_model_set_source: negative or non-finite amplitude / delay at dof " + std::to_string(d)
-                                   + " of the source boundary");
-    amp[k] = a, tau[k] = td;
+    FUSCHK(upload(A.amp, P.amp, st, "per-entry amplitudes (fus_model_set_source)"));
+    FUSCHK(upload(A.tau, P.tau, st, "per-entry delays (fus_model_set_source)"));
+    HIPCHK(hipStreamSynchronize(st));
   }
   // from here on the model changes
-  signal_free(m);   // (leaving the sampled signals, if they were on)
-  if (!m->d_src_base)
+  source_install(m, A, P);
+  if (fold)
   {
-    HIPCHK(hipMalloc(&m->d_src_base, std::max<size_t>(bytes, 16)));
-    if (nb > 0)
-      FUSCHK(copy(m->d_src_base, m->d_bsrc, bytes, hipMemcpyDeviceToDevice));
-    if (m->d_bsrc2)
-    {
-      HIPCHK(hipMalloc(&m->d_src_base2, std::max<size_t>(bytes, 16)));
-      if (nb > 0)
-        FUSCHK(copy(m->d_src_base2, m->d_bsrc2, bytes, hipMemcpyDeviceToDevice));
-    }
+    std::vector<T> w(P.base.size()), w2(P.base2.size());
+    for (size_t k = 0; k < w.size(); ++k)
+      w[k] = P.base[k] * P.amp[k];
+    for (size_t k = 0; k < w2.size(); ++k)
+      w2[k] = P.base2[k] * P.amp[k];
+    FUSCHK(copy_sync(st, B.d_bsrc.p, w.data(), bytes, hipMemcpyHostToDevice));
+    FUSCHK(copy_sync(st, B.d_bsrc2.p, w2.data(), bytes2, hipMemcpyHostToDevice));
   }
-  if (!delay && duration == 0.0)
-  {
-    // amplitude only: folded into the weights once, the scalar path stays
-    std::vector<T> w(nb), w2(base2.size());
-    for (int64_t k = 0; k < nb; ++k)
-      w[k] = base[k] * amp[k];
-    for (size_t k = 0; k < base2.size(); ++k)
-      w2[k] = base2[k] * amp[k];
-    if (nb > 0)
-      FUSCHK(copy(m->d_bsrc, w.data(), bytes, hipMemcpyHostToDevice));
-    if (nb > 0 && m->d_bsrc2)
-      FUSCHK(copy(m->d_bsrc2, w2.data(), bytes, hipMemcpyHostToDevice));
-    m->src_mode = 1, m->src_dur = 0.0;
-  }
-  else
-  {
-    for (void** q : {&m->d_src_amp, &m->d_src_tau})
-      if (!*q)
-        HIPCHK(hipMalloc(q, std::max<size_t>(bytes, 16)));
-    if (nb > 0)
-    {
-      FUSCHK(copy(m->d_src_amp, amp.data(), bytes, hipMemcpyHostToDevice));
-      FUSCHK(copy(m->d_src_tau, tau.data(), bytes, hipMemcpyHostToDevice));
-    }
-    m->src_mode = 2, m->src_dur = duration;
-  }
-  changed();
+  S.mode = fold ? 1 : 2, S.dur = fold ? 0.0 : duration;
+  model_changed(m, CHANGED_SOURCE);
   return FUS_OK;
 }
 
@@ -944,20 +926,12 @@ template <typename T>
 static int model_set_source_weights(fus_model* m, const void* weights, int space)
 {
   fus_op* op = m->op;
-  hipStream_t st = m->ctx->stream;
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<T> vol;
-  if (weights)
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  std::vector<T> vol, hbuf;
+  const T* w;
+  FUSCHK(caller_on_host(m, weights, space, hbuf, &w));
+  if (w)
   {
-    std::vector<T> hbuf;
-    const T* w = static_cast<const T*>(weights);
-    if (space == FUS_DEVICE)
-    {
-      hbuf.resize(op->ndofs);
-      HIPCHK(hipMemcpyAsync(hbuf.data(), weights, (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      w = hbuf.data();
-    }
     for (int64_t d = 0; d < op->ndofs; ++d)
       if (!std::isfinite((double)w[d]))
         return fail(FUS_ERR_ARG, "fus_model_set_source_weights: non-finite weight at dof " + std::to_string(d));
@@ -965,12 +939,11 @@ static int model_set_source_weights(fus_model* m, const void* weights, int space
     for (int64_t d = 0; d < op->ndofs; ++d)
       vol[op->L.dof_perm[d]] = w[d];
   }
-  // from here on the model changes: the default source function on the new entry lists
-  source_free(m);
-  m->src_mode = 0, m->src_dur = 0.0;
-  FUSCHK(model_build_entries<T>(m, weights ? vol.data() : nullptr));
-  m->bnd_valid = false, m->gsteps = 0;
-  m->src_tn_int = m->src_tn_sh = NAN;
+  FUSCHK(model_build_entries<T>(m, w ? vol.data() : nullptr));
+  // the new lists are in force: the default source function on them (the per-entry arrays were in the old lists' order)
+  m->src.d = {};
+  m->src.mode = 0, m->src.dur = 0.0;
+  model_changed(m, CHANGED_SOURCE);
   return FUS_OK;
 }
 
@@ -980,61 +953,27 @@ static int model_set_source_signals(fus_model* m, int64_t nchan, int64_t nsamp, 
                                     const double* signals, const int32_t* channel, const void* amplitude,
                                     const void* delay, int space)
 {
-  fus_op* op = m->op;
   hipStream_t st = m->ctx->stream;
-  const int64_t nb = m->nb;
-  const size_t bytes = (size_t)nb * sizeof(T);
+  const int64_t nb = m->bnd.nb;
   HIPCHK(hipStreamSynchronize(st));
-  auto copy = [&](void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) -> int
-  {
-    HIPCHK(hipMemcpyAsync(dst, src, nbytes, kind, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return FUS_OK;
-  };
   for (int64_t i = 0; i < nchan * nsamp; ++i)
     if (!std::isfinite(signals[i]))
       return fail(FUS_ERR_ARG, "fus_model_set_source_signals: non-finite sample " + std::to_string(i % nsamp) + " of channel "
                                    + std::to_string(i / nsamp));
-  // the source weights and the entries' internal indices, as the setup (or fus_model_set_source_weights) left them
-  std::vector<int32_t> bidx(nb);
-  std::vector<T> base(nb), base2(m->d_bsrc2 ? nb : 0);
-  if (nb > 0)
-  {
-    FUSCHK(copy(bidx.data(), m->d_bidx, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
-    FUSCHK(copy(base.data(), m->d_src_base ? m->d_src_base : m->d_bsrc, bytes, hipMemcpyDeviceToHost));
-    if (m->d_bsrc2)
-      FUSCHK(copy(base2.data(), m->d_src_base2 ? m->d_src_base2 : m->d_bsrc2, bytes, hipMemcpyDeviceToHost));
-  }
-  std::vector<T> hbuf[2];
-  const T* h[2] = {static_cast<const T*>(amplitude), static_cast<const T*>(delay)};
-  for (int j = 0; j < 2; ++j)
-    if (h[j] && space == FUS_DEVICE)
-    {
-      hbuf[j].resize(op->ndofs);
-      FUSCHK(copy(hbuf[j].data(), h[j], (size_t)op->ndofs * sizeof(T), hipMemcpyDeviceToHost));
-      h[j] = hbuf[j].data();
-    }
-  // gather through dof_perm into entry order; only the entries with a source weight count.  The channels are
-  // renumbered in order of first use along the entry list (k_source_entries_signal: rows read contiguously)
-  std::vector<int32_t> caller(op->L.n_internal, -1);
-  for (int64_t d = 0; d < op->ndofs; ++d)
-    caller[op->L.dof_perm[d]] = (int32_t)d;
-  std::vector<T> amp(nb, T(0)), tau(nb, T(0));
+  SourcePrep<T> P;
+  FUSCHK(source_prepare<T>(m, "fus_model_set_source_signals", amplitude, delay, space, &P));
+  // the channels of the entries with a source weight, renumbered in order of first use along the entry list
+  // (k_source_entries_signal: rows read contiguously)
   std::vector<int32_t> chan(nb, -1), renum(nchan, -1), used;
   for (int64_t k = 0; k < nb; ++k)
   {
-    if (base[k] == T(0) && (base2.empty() || base2[k] == T(0)))
+    const int32_t d = P.dof[k];
+    if (d < 0)
       continue;
-    const int32_t d = caller[bidx[k]];
-    const T a = h[0] ? h[0][d] : T(1), td = h[1] ? h[1][d] : T(0);
-    if (!std::isfinite((double)a) || a < T(0) || !std::isfinite((double)td) || td < T(0))
-      return fail(FUS_ERR_ARG, "fus_model_set_source_signals: negative or non-finite amplitude / delay at dof "
-                                   + std::to_string(d) + " of the source");
     const int32_t c = channel ? channel[d] : 0;
     if (c < -1 || c >= nchan)
       return fail(FUS_ERR_ARG, "fus_model_set_source_signals: channel " + std::to_string(c) + " at dof " + std::to_string(d)
                                    + " is neither -1 nor in [0, nchan)");
-    amp[k] = a, tau[k] = td;
     if (c < 0)
       continue;
     if (renum[c] < 0)
@@ -1047,102 +986,50 @@ static int model_set_source_signals(fus_model* m, int64_t nchan, int64_t nsamp, 
     for (int64_t j = 0; j < nsamp; ++j)
       table[(size_t)j * ncu + c] = signals[(size_t)used[c] * nsamp + j];
   // the new arrays first: a failed allocation leaves the source as it was
-  void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // table, chan, base, base2, amp, tau
-  const size_t want[6] = {table.size() * sizeof(double), (size_t)nb * sizeof(int32_t),
-                          m->d_src_base ? 0 : bytes, (m->d_src_base || !m->d_bsrc2) ? 0 : bytes,
-                          m->d_src_amp ? 0 : bytes, m->d_src_tau ? 0 : bytes};
-  const bool need[6] = {true, true, !m->d_src_base, !m->d_src_base && m->d_bsrc2, !m->d_src_amp, !m->d_src_tau};
-  for (int j = 0; j < 6; ++j)
-  {
-    if (!need[j])
-      continue;
-    const hipError_t e = hipMalloc(&fresh[j], std::max<size_t>(want[j], 16));
-    if (e != hipSuccess)
-    {
-      (void)hipGetLastError();
-      for (int i = 0; i < j; ++i)
-        if (fresh[i])
-          (void)hipFree(fresh[i]);
-      return fail(FUS_ERR_HIP, "fus_model_set_source_signals: cannot allocate " + std::to_string(std::max<size_t>(want[j], 16))
-                                   + " bytes" + (j == 0 ? " of sample table: " : ": ") + hipGetErrorString(e));
-    }
-  }
+  ModelSource::Arrays A;
+  FUSCHK(upload(A.table, table, st, "sample table (fus_model_set_source_signals)"));
+  FUSCHK(upload(A.chan, chan, st, "channel list (fus_model_set_source_signals)"));
+  FUSCHK(upload(A.amp, P.amp, st, "per-entry amplitudes (fus_model_set_source_signals)"));
+  FUSCHK(upload(A.tau, P.tau, st, "per-entry delays (fus_model_set_source_signals)"));
+  HIPCHK(hipStreamSynchronize(st));
   // from here on the model changes
-  signal_free(m);
-  m->d_src_table = static_cast<double*>(fresh[0]), m->d_src_chan = static_cast<int32_t*>(fresh[1]);
-  if (need[2])
-  {
-    m->d_src_base = fresh[2];
-    if (nb > 0)
-      FUSCHK(copy(m->d_src_base, m->d_bsrc, bytes, hipMemcpyDeviceToDevice));
-  }
-  if (need[3])
-  {
-    m->d_src_base2 = fresh[3];
-    if (nb > 0)
-      FUSCHK(copy(m->d_src_base2, m->d_bsrc2, bytes, hipMemcpyDeviceToDevice));
-  }
-  if (need[4])
-    m->d_src_amp = fresh[4];
-  if (need[5])
-    m->d_src_tau = fresh[5];
-  FUSCHK(copy(m->d_src_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (nb > 0)
-  {
-    FUSCHK(copy(m->d_src_chan, chan.data(), (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice));
-    FUSCHK(copy(m->d_src_amp, amp.data(), bytes, hipMemcpyHostToDevice));
-    FUSCHK(copy(m->d_src_tau, tau.data(), bytes, hipMemcpyHostToDevice));
-  }
-  m->src_sig = SourceSignal{t_first, ds, nsamp, ncu};
-  m->src_mode = 3, m->src_dur = 0.0;
-  m->bnd_valid = false, m->gsteps = 0;
-  m->src_tn_int = m->src_tn_sh = NAN;
+  source_install(m, A, P);
+  m->src.sig = SourceSignal{t_first, ds, nsamp, ncu};
+  m->src.mode = 3, m->src.dur = 0.0;
+  model_changed(m, CHANGED_SOURCE);
   return FUS_OK;
 }
 
 // ---- receivers: point samples of the resident solution (reference: Function::eval at located cells,
 // python/src/fenicsxfus/utils.py:10-47, cpp/mwe/parallel_eval_line/main.cpp:49-84) ----
-static void launch_sample(fus_model* m, int which, void* out)
+template <typename T>
+static int launch_sample(fus_model* m, int which, void* out)
 {
   fus_op* op = m->op;
-  const void* vec = which == FUS_U ? m->u0 : m->v0;
-  const dim3 grid((unsigned)((m->rc_n + 3) / 4)), blockd(256);
-  hipStream_t st = m->ctx->stream;
-#define FUS_SAMPLE(T, TD)                                                                          \
-  hipLaunchKernelGGL((k_sample<T, TD>), grid, blockd, 0, st, m->rc_n, op->N, m->d_rc_idx,          \
-                     static_cast<const T*>(m->d_rc_bas), static_cast<const T*>(vec), static_cast<T*>(out))
-  if (op->dtype == FUS_F64)
+  const T* vec = static_cast<const T*>(which == FUS_U ? m->u0 : m->v0);
+  const dim3 grid((unsigned)((m->rc.n + 3) / 4)), blockd(256);
+  return with_kind<2, 3>(op->tdim, [&](auto TD) -> int
   {
-    if (op->tdim == 3)
-      FUS_SAMPLE(double, 3);
-    else
-      FUS_SAMPLE(double, 2);
-  }
-  else
-  {
-    if (op->tdim == 3)
-      FUS_SAMPLE(float, 3);
-    else
-      FUS_SAMPLE(float, 2);
-  }
-#undef FUS_SAMPLE
+    hipLaunchKernelGGL((k_sample<T, decltype(TD)::value>), grid, blockd, 0, m->ctx->stream, m->rc.n, op->N, m->rc.d_idx.as<int32_t>(),
+                       m->rc.d_bas.as<const T>(), vec, static_cast<T*>(out));
+    HIPCHK(hipGetLastError());
+    return FUS_OK;
+  });
 }
 
 // after a step that ended at time t: every rec_every-th step, one sample of the receivers into the record buffer
 static int model_record_step(fus_model* m, double t)
 {
-  if (m->rec_every <= 0)
+  if (m->rc.rec_every <= 0)
     return FUS_OK;
-  ++m->rec_step;
-  if (m->rec_step % m->rec_every != 0 || m->rec_n >= m->rec_cap)
+  ++m->rc.rec_step;
+  if (m->rc.rec_step % m->rc.rec_every != 0 || m->rc.rec_n >= m->rc.rec_cap)
     return FUS_OK;
-  if (m->rc_n > 0)  // a rank that holds none of the receivers still counts the record and its time
-  {
-    launch_sample(m, m->rec_which, static_cast<char*>(m->d_rec) + (size_t)m->rec_n * m->rc_n * m->op->ts);
-    HIPCHK(hipGetLastError());
-  }
-  m->rec_times.push_back(t);
-  ++m->rec_n;
+  if (m->rc.n > 0)  // a rank that holds none of the receivers still counts the record and its time
+    FUSCHK(FUS_BY_DTYPE(m->op->dtype, launch_sample, m, m->rc.rec_which,
+                        m->rc.d_rec.as<char>() + (size_t)m->rc.rec_n * m->rc.n * m->op->ts));
+  m->rc.rec_times.push_back(t);
+  ++m->rc.rec_n;
   return FUS_OK;
 }
 
@@ -1158,26 +1045,26 @@ static size_t monitor_bytes(const fus_model* m, int nharm)
 // like the stage calls of its loop, with the device that is current -- the members of a group share one device.
 static int model_after_step(fus_model* m, double t)
 {
-  if (m->mon_every <= 0)
+  if (m->mon.every <= 0)
     return FUS_OK;
-  const int64_t s = ++m->mon_step;
-  if (s <= m->mon_skip || (s - m->mon_skip) % m->mon_every != 0 || (m->mon_count > 0 && m->mon_n >= m->mon_count))
+  const int64_t s = ++m->mon.step;
+  if (s <= m->mon.skip || (s - m->mon.skip) % m->mon.every != 0 || (m->mon.count > 0 && m->mon.n >= m->mon.count))
     return FUS_OK;
   double c[8], sn[8];
-  for (int k = 1; k <= m->mon_nharm; ++k)
+  for (int k = 1; k <= m->mon.nharm; ++k)
   {
-    const double arg = 2.0 * M_PI * k * m->mon_freq * t;
+    const double arg = 2.0 * M_PI * k * m->mon.freq * t;
     c[k - 1] = std::cos(arg), sn[k - 1] = std::sin(arg);
   }
   {
     ProfScope ps(m->ctx, "monitor");
-    FUS_BY_DTYPE(m->op->dtype, launch_monitor_nh, m, c, sn);
+    FUSCHK(FUS_BY_DTYPE(m->op->dtype, launch_monitor_nh, m, c, sn));
   }
   HIPCHK(hipGetLastError());
-  if (m->mon_n == 0)
-    m->mon_t_first = t;
-  m->mon_t_last = t;
-  ++m->mon_n;
+  if (m->mon.n == 0)
+    m->mon.t_first = t;
+  m->mon.t_last = t;
+  ++m->mon.n;
   return FUS_OK;
 }
 
@@ -1387,11 +1274,7 @@ int fus_model_create(fus_ctx* c, int kind, fus_op* op, const void* c0, const voi
       r = d_setup_finish(m.get());
   }
   if (r != FUS_OK)
-  {
-    for (void* q : m->allocs)
-      (void)hipFree(q);
-    return r;
-  }
+    return r;   // (m frees what the setup had allocated)
   *out = m.release();
   return FUS_OK;
 }
@@ -1485,7 +1368,7 @@ int fus_model_set_rk_order(fus_model* m, int order)
   if (!m || order < 1 || order > 4)
     return fail(FUS_ERR_ARG, "rk order must be 1, 2, 3 or 4");
   m->rk_order = order;
-  m->bnd_valid = false;
+  model_changed(m, CHANGED_ORDER);
   return FUS_OK;
 }
 
@@ -1499,12 +1382,7 @@ int fus_model_destroy(fus_model* m)
     (void)hipGraphExecDestroy(m->gexec);
   if (m->op && m->op->bnd_owner == m)
     m->op->bnd_owner = nullptr;
-  for (void* q : m->allocs)
-    (void)hipFree(q);
-  if (m->d_mon)
-    (void)hipFree(m->d_mon);
-  source_free(m);
-  delete m;
+  delete m;   // frees its arrays: nothing on the stream reads them any more
   return FUS_OK;
 }
 
@@ -1517,8 +1395,7 @@ int fus_model_init(fus_model* m)
   for (void* v : {m->u0, m->v0, m->u_, m->v_, m->un, m->vn, m->b})
     HIPCHK(hipMemsetAsync(v, 0, bytes, m->ctx->stream));
   m->initialised = true;
-  m->bnd_valid = false;  // state changed: the pseudo boundary partials are stale
-  m->gsteps = 0;
+  model_changed(m, CHANGED_STATE);
   return FUS_OK;
 }
 
@@ -1555,25 +1432,23 @@ int fus_model_set_receivers(fus_model* m, int64_t npts, const int32_t* cells, co
   }
   hipStream_t st = m->ctx->stream;
   HIPCHK(hipStreamSynchronize(st));
-  m->rc_n = npts;
-  m->rec_every = 0, m->rec_n = 0, m->rec_cap = 0, m->rec_alloc = 0, m->rec_times.clear();
-  FUSCHK(upload(m->allocs, &m->d_rc_idx, idx, st));
+  // the new receivers beside those in force; they replace them, and drop the records taken at the old points, at the end
+  ModelReceivers R;
+  const char* what = "receiver arrays (fus_model_set_receivers)";
+  R.n = npts;
+  FUSCHK(upload(R.d_idx, idx, st, what));
   if (op->dtype == FUS_F64)
-  {
-    double* q = nullptr;
-    FUSCHK(upload(m->allocs, &q, bas, st));
-    m->d_rc_bas = q;
-  }
+    FUSCHK(upload(R.d_bas, bas, st, what));
   else
   {
-    std::vector<float> bf(bas.begin(), bas.end());
-    float* q = nullptr;
-    FUSCHK(upload(m->allocs, &q, bf, st));
-    m->d_rc_bas = q;
+    const std::vector<float> bf(bas.begin(), bas.end());
+    FUSCHK(upload(R.d_bas, bf, st, what));
     HIPCHK(hipStreamSynchronize(st));  // bf leaves scope
   }
-  FUSCHK(dalloc_bytes(m->allocs, &m->d_rc_out, (size_t)npts * op->ts, true, st));
-  HIPCHK(hipStreamSynchronize(st));
+  FUSCHK(R.d_out.alloc((size_t)npts * op->ts, what));
+  HIPCHK(hipMemsetAsync(R.d_out.p, 0, std::max<size_t>(R.d_out.bytes, 16), st));
+  HIPCHK(hipStreamSynchronize(st));   // the host vectors leave scope
+  m->rc = std::move(R);
   return FUS_OK;
 }
 
@@ -1581,14 +1456,13 @@ int fus_model_sample(fus_model* m, int which, void* out, int space)
 {
   if (!m || !out || (which != FUS_U && which != FUS_V))
     return fail(FUS_ERR_ARG, "bad argument");
-  if (m->rc_n == 0)
-    return m->d_rc_idx ? FUS_OK : fail(FUS_ERR_STATE, "fus_model_set_receivers has not been called");
+  if (m->rc.n == 0)
+    return m->rc.d_idx ? FUS_OK : fail(FUS_ERR_STATE, "fus_model_set_receivers has not been called");
   HIPCHK(hipSetDevice(m->ctx->device));
   hipStream_t st = m->ctx->stream;
-  launch_sample(m, which, space == FUS_HOST ? m->d_rc_out : out);
-  HIPCHK(hipGetLastError());
+  FUSCHK(FUS_BY_DTYPE(m->op->dtype, launch_sample, m, which, space == FUS_HOST ? m->rc.d_out.p : out));
   if (space == FUS_HOST)
-    HIPCHK(hipMemcpyAsync(out, m->d_rc_out, (size_t)m->rc_n * m->op->ts, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out, m->rc.d_out.p, (size_t)m->rc.n * m->op->ts, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return FUS_OK;
 }
@@ -1597,18 +1471,19 @@ int fus_model_record(fus_model* m, int which, int every, int64_t capacity)
 {
   if (!m || (which != FUS_U && which != FUS_V) || every < 0 || capacity < 0)
     return fail(FUS_ERR_ARG, "bad argument");
-  if (every > 0 && !m->d_rc_idx)
+  if (every > 0 && !m->rc.d_idx)
     return fail(FUS_ERR_STATE, "fus_model_set_receivers has not been called");
   HIPCHK(hipSetDevice(m->ctx->device));
-  m->rec_every = every, m->rec_which = which, m->rec_n = 0, m->rec_step = 0, m->rec_times.clear();
+  m->rc.rec_every = every, m->rc.rec_which = which, m->rc.rec_n = 0, m->rc.rec_step = 0, m->rc.rec_times.clear();
   if (every > 0)
   {
-    if (capacity > m->rec_alloc)
+    const size_t need = (size_t)capacity * std::max<int64_t>(m->rc.n, 1) * m->op->ts;
+    if (need > m->rc.d_rec.bytes)   // it only grows: the records of the recording before go with the old buffer
     {
-      FUSCHK(dalloc_bytes(m->allocs, &m->d_rec, (size_t)capacity * std::max<int64_t>(m->rc_n, 1) * m->op->ts, false, m->ctx->stream));
-      m->rec_alloc = capacity;
+      HIPCHK(hipStreamSynchronize(m->ctx->stream));
+      FUSCHK(m->rc.d_rec.alloc(need, "record buffer (fus_model_record)"));
     }
-    m->rec_cap = capacity;  // the limit of this recording, whatever an earlier one allocated
+    m->rc.rec_cap = capacity;  // the limit of this recording, whatever an earlier one allocated
   }
   return FUS_OK;
 }
@@ -1618,15 +1493,15 @@ int fus_model_get_records(fus_model* m, void* out, double* times, int64_t* nrec)
   if (!m || !nrec)
     return fail(FUS_ERR_ARG, "bad argument");
   HIPCHK(hipSetDevice(m->ctx->device));
-  const int64_t n = m->rec_n;
-  if (out && n > 0 && m->rc_n > 0)
+  const int64_t n = m->rc.rec_n;
+  if (out && n > 0 && m->rc.n > 0)
   {
-    HIPCHK(hipMemcpyAsync(out, m->d_rec, (size_t)n * m->rc_n * m->op->ts, hipMemcpyDeviceToHost, m->ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, m->rc.d_rec.p, (size_t)n * m->rc.n * m->op->ts, hipMemcpyDeviceToHost, m->ctx->stream));
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
   }
   if (times)
     for (int64_t k = 0; k < n; ++k)
-      times[k] = m->rec_times[k];
+      times[k] = m->rc.rec_times[k];
   *nrec = n;
   return FUS_OK;
 }
@@ -1639,35 +1514,24 @@ int fus_model_monitor(fus_model* m, int which, int nharm, double freq, int64_t s
   if (every == 0)
   {
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    if (m->d_mon)
-      (void)hipFree(m->d_mon);
-    m->d_mon = nullptr, m->mon_bytes = 0, m->mon_every = 0, m->mon_n = 0, m->mon_step = 0;
+    m->mon.d_mon.reset();
+    m->mon.every = 0, m->mon.n = 0, m->mon.step = 0;
     return FUS_OK;
   }
   if ((which != FUS_U && which != FUS_V) || nharm < 0 || nharm > 8 || every < 0 || skip < 0 || count < 0
       || !(freq >= 0.0) || !std::isfinite(freq))
     return fail(FUS_ERR_ARG, "fus_model_monitor: which is FUS_U | FUS_V, nharm 0..8, freq >= 0, skip >= 0, every > 0 (0: off), count >= 0");
   const size_t bytes = monitor_bytes(m, nharm);
-  if (bytes != m->mon_bytes)
+  if (bytes != m->mon.d_mon.bytes)
   {
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    if (m->d_mon)
-      (void)hipFree(m->d_mon);
-    m->d_mon = nullptr, m->mon_bytes = 0, m->mon_every = 0;
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess)
-    {
-      (void)hipGetLastError();
-      return fail(FUS_ERR_HIP, "fus_model_monitor: cannot allocate " + std::to_string(bytes)
-                                   + " bytes of accumulators: " + hipGetErrorString(e));
-    }
-    m->d_mon = q, m->mon_bytes = bytes;
+    m->mon.every = 0;   // off, should the allocation fail
+    FUSCHK(m->mon.d_mon.alloc(bytes, "monitor accumulators (fus_model_monitor)"));
   }
-  HIPCHK(hipMemsetAsync(m->d_mon, 0, bytes, m->ctx->stream));
-  m->mon_which = which, m->mon_nharm = nharm, m->mon_freq = freq == 0.0 ? m->freq : freq;
-  m->mon_skip = skip, m->mon_every = every, m->mon_count = count;
-  m->mon_step = 0, m->mon_n = 0, m->mon_t_first = m->mon_t_last = 0.0;
+  HIPCHK(hipMemsetAsync(m->mon.d_mon.p, 0, bytes, m->ctx->stream));
+  m->mon.which = which, m->mon.nharm = nharm, m->mon.freq = freq == 0.0 ? m->freq : freq;
+  m->mon.skip = skip, m->mon.every = every, m->mon.count = count;
+  m->mon.step = 0, m->mon.n = 0, m->mon.t_first = m->mon.t_last = 0.0;
   return FUS_OK;
 }
 
@@ -1675,14 +1539,14 @@ int fus_model_monitor_info(fus_model* m, int64_t* nsamples, double* t_first, dou
 {
   if (!m)
     return fail(FUS_ERR_ARG, "null model");
-  if (m->mon_every <= 0)
+  if (m->mon.every <= 0)
     return fail(FUS_ERR_STATE, "the monitor is off (fus_model_monitor)");
   if (nsamples)
-    *nsamples = m->mon_n;
+    *nsamples = m->mon.n;
   if (t_first)
-    *t_first = m->mon_t_first;
+    *t_first = m->mon.t_first;
   if (t_last)
-    *t_last = m->mon_t_last;
+    *t_last = m->mon.t_last;
   return FUS_OK;
 }
 
@@ -1690,11 +1554,11 @@ int fus_model_monitor_get(fus_model* m, int quantity, int k, void* out, int spac
 {
   if (!m || !out || quantity < FUS_MON_MAX || quantity > FUS_MON_SIN || (space != FUS_HOST && space != FUS_DEVICE))
     return fail(FUS_ERR_ARG, "fus_model_monitor_get: bad model, quantity, out or space");
-  if (m->mon_every <= 0)
+  if (m->mon.every <= 0)
     return fail(FUS_ERR_STATE, "the monitor is off (fus_model_monitor)");
-  if ((quantity == FUS_MON_COS || quantity == FUS_MON_SIN) && (k < 1 || k > m->mon_nharm))
+  if ((quantity == FUS_MON_COS || quantity == FUS_MON_SIN) && (k < 1 || k > m->mon.nharm))
     return fail(FUS_ERR_ARG, "fus_model_monitor_get: harmonic k outside 1..nharm");
-  if (m->mon_n == 0)
+  if (m->mon.n == 0)
     return fail(FUS_ERR_STATE, "the monitor has taken no sample yet");
   HIPCHK(hipSetDevice(m->ctx->device));
   return FUS_BY_DTYPE(m->op->dtype, monitor_get, m, quantity, k, out, space);
@@ -1751,8 +1615,7 @@ int fus_model_set(fus_model* m, int which, const void* in, int space)
     return fail(FUS_ERR_ARG, "bad argument");
   HIPCHK(hipSetDevice(m->ctx->device));
   m->initialised = true;
-  m->bnd_valid = false;  // state changed: the pseudo boundary partials are stale
-  m->gsteps = 0;
+  model_changed(m, CHANGED_STATE);
   return FUS_BY_DTYPE(m->op->dtype, model_getset, m, which == FUS_U ? m->u0 : m->v0, const_cast<void*>(in), space, true);
 }
 
