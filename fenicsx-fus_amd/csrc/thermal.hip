@@ -8,6 +8,7 @@
 #include "thermal_bc.hpp"
 #include "thermal_kernels.hpp"
 #include "thermal_owner.hpp"
+#include "thermal_response.hpp"
 
 using namespace fus;
 
@@ -58,6 +59,16 @@ struct fus_thermal
   // sharers starts from it whenever any member of the group sets a boundary
   std::vector<uint8_t> rq_fixed;
   std::vector<char> rq_rise, rq_diag, rq_crise;
+  // perfusion response and damage (fusmi.h "bioheat", perfusion response and damage; laws: thermal_response.hpp).  While a
+  // response is set the stage kernels read mweff = m_W .* phi(theta_n, D_n) in place of mw; k_thermal_response rewrites it
+  // after every step, together with Omega and r_prev, the damage rate at the state it saw.  respond_dirty: the state, the
+  // response or the boundary changed since that kernel ran last, so the next steps call (or a read of the perfusion plane)
+  // starts with a launch of it that only primes mweff and r_prev.
+  fus::ThermalResponse resp;
+  fus::ThermalDamage dmg;
+  void* mweff = nullptr;   // T, n_internal: allocated by the first fus_thermal_set_response that sets a law
+  DevBuf omega, rprev;     // double, n_internal: held while the damage is on
+  bool respond_dirty = true;
 };
 
 static bool thermal_multi(const fus_thermal* th) { return !th->op->neigh.empty(); }
@@ -83,6 +94,9 @@ static int thermal_sum(fus_thermal** ths, int n, void* (*vec)(fus_thermal*))
 
 // 1 / m_C as the stage and power kernels take it: zero at the fixed DOFs while there are any
 static const void* thermal_minv(const fus_thermal* th) { return th->bc.nfix > 0 ? th->minv_bc : th->minv; }
+
+// the perfusion plane as the stage kernels take it: m_W itself while no response is set
+static const void* thermal_mw(const fus_thermal* th) { return th->resp.active() ? th->mweff : th->mw; }
 
 // b += r - m_H x at the convective DOFs (r_too = false: the homogeneous part); nothing is enqueued without such DOFs
 template <typename T>
@@ -215,6 +229,39 @@ static unsigned thermal_grid(const fus_thermal* th, int64_t* nvec, bool local = 
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((*nvec + 255) / 256, (int64_t)th->ctx->num_cus * 8));
 }
 
+// The launch behind the perfusion response and the damage (k_thermal_response), over all n_internal slots: after a step of
+// size dt, or (prime) before the first step after something it reads from changed.  Nothing is enqueued while both are off.
+template <typename T>
+static int thermal_respond(fus_thermal* th, double dt, bool prime)
+{
+  const int mode = (th->resp.active() ? 1 : 0) | (th->dmg.on() ? 2 : 0);
+  if (mode == 0)
+    return FUS_OK;
+  ThermalRespond<T> A;
+  A.th = static_cast<const T*>(th->th0), A.dose = th->dose, A.mw = static_cast<const T*>(th->mw);
+  A.mweff = static_cast<T*>(th->mweff), A.omega = th->omega.as<double>(), A.rprev = th->rprev.as<double>();
+  A.R = th->resp, A.lnA = th->dmg.lnA, A.Ea = th->dmg.Ea, A.dt2 = dt / 2.0, A.t_base = th->t_base;
+  A.prime = prime ? 1 : 0;
+  int64_t nvec;
+  const unsigned grid = thermal_grid<T>(th, &nvec);
+  ProfScope ps(th->ctx, "thermal_response");
+  return with_kind<1, 2, 3>(mode, [&](auto M) -> int
+  {
+    hipLaunchKernelGGL((k_thermal_response<T, decltype(M)::value>), dim3(grid), dim3(256), 0, th->ctx->stream, nvec, A);
+    HIPCHK(hipGetLastError());
+    return FUS_OK;
+  });
+}
+
+template <typename T>
+static int thermal_prime(fus_thermal* th)
+{
+  if (th->respond_dirty)
+    FUSCHK(thermal_respond<T>(th, 0.0, true));
+  th->respond_dirty = false;
+  return FUS_OK;
+}
+
 // First half of a stage of either scheme: b = K(-k) x, the convective term, and on several ranks the pack of this rank's
 // totals of the interface DOFs into the send buffer (the event hands it to the exchange)
 template <typename T>
@@ -292,7 +339,7 @@ static int thermal_rk4_end(fus_thermal* th, int i, double dt_, double sigma)
   A.b = static_cast<const T*>(th->b), A.th_in = static_cast<const T*>(thermal_rk4_input(th, i));
   A.th_out = static_cast<T*>(i == 3 ? th->th0 : th->ths);
   A.th0 = static_cast<const T*>(th->th0), A.acc = static_cast<T*>(th->acc);
-  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(thermal_mw(th)), A.h = static_cast<const T*>(th->h);
   A.dose = th->dose;
   A.adt = dt * a_next[i], A.bdt = dt * b_runge[i], A.sigma = (T)sigma;
   A.dt60 = dt_ / 60.0, A.t_base = th->t_base;
@@ -315,7 +362,7 @@ static int thermal_sts_end(fus_thermal* th, int j, double dt_, double sigma, con
   A.y2 = j <= 2 ? th0 : rot[(j - 1) & 1];
   A.y0 = th0, A.f0 = static_cast<T*>(th->f0);
   A.out = j == c.s ? th0 : rot[(j - 1) & 1];
-  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(th->mw), A.h = static_cast<const T*>(th->h);
+  A.minv = static_cast<const T*>(thermal_minv(th)), A.mw = static_cast<const T*>(thermal_mw(th)), A.h = static_cast<const T*>(th->h);
   A.dose = th->dose;
   A.mu = (T)c.mu[j], A.nu = (T)c.nu[j], A.om = (T)(1.0 - c.mu[j] - c.nu[j]);
   A.mdt = (T)(c.mut[j] * dt_), A.gdt = (T)(c.gat[j] * dt_), A.sigma = (T)sigma;
@@ -336,6 +383,8 @@ static int thermal_run(fus_thermal** ths, int n, double dt, int64_t nsteps, doub
   std::vector<fus_op*> ops(n);
   for (int i = 0; i < n; ++i)
     ops[i] = ths[i]->op;
+  for (int i = 0; i < n; ++i)
+    FUSCHK(thermal_prime<T>(ths[i]));
   for (int64_t s = 0; s < nsteps; ++s)
   {
     for (int st = 0; st < (stages == 0 ? 4 : stages); ++st)
@@ -357,6 +406,9 @@ static int thermal_run(fus_thermal** ths, int n, double dt, int64_t nsteps, doub
     if (stages != 0)
       for (int i = 0; i < n; ++i)
         FUSCHK(thermal_impose<T>(ths[i], ths[i]->th0));
+    // phi of the next step from (theta_{n+1}, D_{n+1}), and the damage of this one
+    for (int i = 0; i < n; ++i)
+      FUSCHK(thermal_respond<T>(ths[i], dt, false));
   }
   for (int i = 0; i < n; ++i)
     HIPCHK(hipStreamSynchronize(ths[i]->ctx->stream));
@@ -545,8 +597,9 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
   fus_op* op = th->op;
   hipStream_t st = th->ctx->stream;
   const int64_t nd = op->ndofs;
-  if (which == FUS_TH_DOSE)
+  if (which == FUS_TH_DOSE || which == FUS_TH_DAMAGE)
   {
+    double* plane = which == FUS_TH_DOSE ? th->dose : th->omega.as<double>();
     double* stg = th->d_stage;
     if (set)
     {
@@ -556,20 +609,21 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
         HIPCHK(hipMemcpyAsync(stg, host_or_dev, nd * sizeof(double), hipMemcpyHostToDevice, st));
         src = stg;
       }
-      hipLaunchKernelGGL((k_to_internal<double>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, src, th->dose);
+      hipLaunchKernelGGL((k_to_internal<double>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm, src, plane);
     }
     else
     {
       double* dst = space == FUS_HOST ? stg : static_cast<double*>(host_or_dev);
       hipLaunchKernelGGL((k_from_internal<double, 0>), dim3(nblk(nd)), dim3(256), 0, st, nd, op->d_dof_perm,
-                         static_cast<const double*>(th->dose), dst);
+                         static_cast<const double*>(plane), dst);
       if (space == FUS_HOST)
         HIPCHK(hipMemcpyAsync(host_or_dev, stg, nd * sizeof(double), hipMemcpyDeviceToHost, st));
     }
   }
   else
   {
-    T* vec = static_cast<T*>(which == FUS_TH_RISE ? th->th0 : th->h);
+    // (the perfusion plane is only read)
+    T* vec = static_cast<T*>(which == FUS_TH_RISE ? th->th0 : (which == FUS_TH_HEAT ? th->h : const_cast<void*>(thermal_mw(th))));
     T* tc = static_cast<T*>(op->d_tmp_c);
     if (set)
     {
@@ -597,7 +651,8 @@ static int thermal_vec(fus_thermal* th, int which, void* host_or_dev, int space,
   return FUS_OK;
 }
 
-// Power iteration for lambda_max of m_C^-1 (K(k) + diag(m_W + m_H)) with the rows and columns of the fixed DOFs removed
+// Power iteration for lambda_max of m_C^-1 (K(k) + diag(phi_max m_W + m_H)) (phi_max: the largest factor of the perfusion
+// response, 1 without one) with the rows and columns of the fixed DOFs removed
 // (the start vector is zero there, and so is every iterate: minv_bc).  Setup-time work: the operator and the quotient
 // y = (K(k) x + m_W x + m_H x) / m_C run on the device, y is pulled, the three m_C-weighted dot products and the normalisation
 // are done on the host in double, and the next x is pushed back.
@@ -672,7 +727,7 @@ static int thermal_lambda_max(fus_thermal** ths, int n, int iters, double* lambd
       Member& m = M[i];
       hipLaunchKernelGGL((k_thermal_power<T>), dim3(1024), dim3(256), 0, st, ni, static_cast<const T*>(th->b),
                          static_cast<const T*>(th->ths), static_cast<const T*>(th->mw),
-                         static_cast<const T*>(thermal_minv(th)), static_cast<T*>(th->acc));
+                         (T)th->resp.phi_max, static_cast<const T*>(thermal_minv(th)), static_cast<T*>(th->acc));
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(m.y.data(), th->acc, ni * sizeof(T), hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
@@ -904,6 +959,16 @@ static int thermal_group(fus_thermal** ths, int n, const char* fn)
   return FUS_OK;
 }
 
+// the members of a group call carry the same response and damage laws
+static int thermal_same_laws(fus_thermal** ths, int n, const char* fn)
+{
+  for (int i = 1; i < n; ++i)
+    if (!ths[i]->resp.same(ths[0]->resp) || !ths[i]->dmg.same(ths[0]->dmg))
+      return fail(FUS_ERR_STATE, std::string(fn) + ": the members differ in their perfusion response or damage parameters; "
+                                                   "call fus_thermal_set_response / fus_thermal_set_damage alike on all of them");
+  return FUS_OK;
+}
+
 static int thermal_step_args(const char* fn, double dt, int64_t nsteps, double heat_scale)
 {
   if (!(dt > 0) || !std::isfinite(dt))
@@ -956,28 +1021,41 @@ int fus_thermal_init(fus_thermal* th)
   for (void* v : {th->th0, th->ths, th->acc})
     HIPCHK(hipMemsetAsync(v, 0, n * th->op->ts, th->ctx->stream));
   HIPCHK(hipMemsetAsync(th->dose, 0, n * sizeof(double), th->ctx->stream));
+  if (th->dmg.on())
+    HIPCHK(hipMemsetAsync(th->omega.p, 0, n * sizeof(double), th->ctx->stream));
   FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_impose, th, th->th0));
   HIPCHK(hipStreamSynchronize(th->ctx->stream));
-  th->initialised = true;
+  th->initialised = th->respond_dirty = true;
   return FUS_OK;
 }
 
 int fus_thermal_set(fus_thermal* th, int which, const void* in, int space)
 {
-  if (!th || !in || (which != FUS_TH_RISE && which != FUS_TH_DOSE) || (space != FUS_HOST && space != FUS_DEVICE))
-    return fail(FUS_ERR_ARG, "fus_thermal_set: null argument, which not FUS_TH_RISE | FUS_TH_DOSE, or bad space");
+  if (!th || !in || (which != FUS_TH_RISE && which != FUS_TH_DOSE && which != FUS_TH_DAMAGE)
+      || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_thermal_set: null argument, which not FUS_TH_RISE | FUS_TH_DOSE | FUS_TH_DAMAGE, or bad space");
+  if (which == FUS_TH_DAMAGE && !th->dmg.on())
+    return fail(FUS_ERR_STATE, "fus_thermal_set: FUS_TH_DAMAGE while the damage is off (fus_thermal_set_damage)");
   FUSCHK(thermal_ready(th, "fus_thermal_set"));
   HIPCHK(hipSetDevice(th->ctx->device));
   FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_vec, th, which, const_cast<void*>(in), space, true));
-  th->initialised = true;
+  th->initialised = th->respond_dirty = true;
   return FUS_OK;
 }
 
 int fus_thermal_get(fus_thermal* th, int which, void* out, int space)
 {
-  if (!th || !out || which < FUS_TH_RISE || which > FUS_TH_HEAT || (space != FUS_HOST && space != FUS_DEVICE))
-    return fail(FUS_ERR_ARG, "fus_thermal_get: null argument, which not FUS_TH_RISE | FUS_TH_DOSE | FUS_TH_HEAT, or bad space");
+  if (!th || !out || which < FUS_TH_RISE || which > FUS_TH_PERFUSION || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_thermal_get: null argument, which not FUS_TH_RISE | FUS_TH_DOSE | FUS_TH_HEAT | FUS_TH_DAMAGE | "
+                             "FUS_TH_PERFUSION, or bad space");
+  if (which == FUS_TH_DAMAGE && !th->dmg.on())
+    return fail(FUS_ERR_STATE, "fus_thermal_get: FUS_TH_DAMAGE while the damage is off (fus_thermal_set_damage)");
   HIPCHK(hipSetDevice(th->ctx->device));
+  if (which == FUS_TH_PERFUSION)   // the plane the next step will use: formed now if the state changed since the last step
+  {
+    FUSCHK(thermal_ready(th, "fus_thermal_get"));
+    FUSCHK(FUS_BY_DTYPE(th->op->dtype, thermal_prime, th));
+  }
   return FUS_BY_DTYPE(th->op->dtype, thermal_vec, th, which, out, space, false);
 }
 
@@ -1105,7 +1183,10 @@ int fus_group_thermal_finish(fus_thermal** ths, int n)
     }
   }
   for (int i = 0; i < n; ++i)
+  {
     HIPCHK(hipStreamSynchronize(ths[i]->ctx->stream));
+    ths[i]->respond_dirty = ths[i]->respond_dirty || any != 0;   // m_W or the fixed values may be new
+  }
   return FUS_OK;
 }
 
@@ -1115,6 +1196,7 @@ int fus_group_thermal_steps(fus_thermal** ths, int n, double dt, int64_t nsteps,
   if (stages != 0 && !fus::sts_stages_ok(stages))
     return fail(FUS_ERR_ARG, "fus_group_thermal_steps: stages must be 0 (RK4) or lie in 2..32");
   FUSCHK(thermal_step_args("fus_group_thermal_steps", dt, nsteps, heat_scale));
+  FUSCHK(thermal_same_laws(ths, n, "fus_group_thermal_steps"));
   for (int i = 0; i < n; ++i)
   {
     FUSCHK(thermal_ready(ths[i], "fus_group_thermal_steps"));
@@ -1135,6 +1217,7 @@ static int thermal_group_lambda(fus_thermal** ths, int n, int iters, const char*
     return fail(FUS_ERR_ARG, std::string(fn) + ": null argument");
   if (iters < 1)
     return fail(FUS_ERR_ARG, std::string(fn) + ": iters must be at least 1");
+  FUSCHK(thermal_same_laws(ths, n, fn));
   for (int i = 0; i < n; ++i)
     FUSCHK(thermal_ready(ths[i], fn));
   HIPCHK(hipSetDevice(ths[0]->ctx->device));
@@ -1170,7 +1253,55 @@ int fus_thermal_set_boundary(fus_thermal* th, const uint8_t* fixed, const void* 
   if (!th)
     return fail(FUS_ERR_ARG, "fus_thermal_set_boundary: null argument");
   HIPCHK(hipSetDevice(th->ctx->device));
+  th->respond_dirty = true;   // theta at the fixed DOFs may be new
   return FUS_BY_DTYPE(th->op->dtype, thermal_set_boundary, th, fixed, fixed_rise, conv_diag, conv_rise);
+}
+
+int fus_thermal_set_response(fus_thermal* th, int nknots, const double* temp, const double* factor, double dose_lo,
+                             double dose_hi)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_response: null argument");
+  fus::ThermalResponse R;
+  const int err = fus::thermal_response_check(nknots, temp, factor, dose_lo, dose_hi, &R);
+  if (err != fus::TRS_OK)
+    return fail(FUS_ERR_ARG, std::string("fus_thermal_set_response: ") + fus::thermal_response_message(err));
+  HIPCHK(hipSetDevice(th->ctx->device));
+  if (R.active() && !th->mweff)
+  {
+    FUSCHK(dalloc_bytes(th->allocs, &th->mweff, th->op->L.n_internal * th->op->ts, true, th->ctx->stream));
+    HIPCHK(hipStreamSynchronize(th->ctx->stream));
+  }
+  th->resp = R;   // every step that read the previous law has finished: the step calls synchronise
+  th->respond_dirty = true;
+  return FUS_OK;
+}
+
+int fus_thermal_set_damage(fus_thermal* th, double A, double Ea)
+{
+  if (!th)
+    return fail(FUS_ERR_ARG, "fus_thermal_set_damage: null argument");
+  fus::ThermalDamage D;
+  const int err = fus::thermal_damage_check(A, Ea, &D);
+  if (err != fus::TRS_OK)
+    return fail(FUS_ERR_ARG, std::string("fus_thermal_set_damage: ") + fus::thermal_response_message(err));
+  HIPCHK(hipSetDevice(th->ctx->device));
+  if (!D.on())
+    th->omega.reset(), th->rprev.reset();
+  else if (!th->dmg.on())   // switched on: Omega = 0; a change of the constants keeps what has accumulated
+  {
+    const size_t bytes = (size_t)th->op->L.n_internal * sizeof(double);
+    DevBuf om, rp;
+    FUSCHK(om.alloc(bytes, "the damage plane (fus_thermal_set_damage)"));
+    FUSCHK(rp.alloc(bytes, "the damage rate plane (fus_thermal_set_damage)"));
+    HIPCHK(hipMemsetAsync(om.p, 0, bytes, th->ctx->stream));
+    HIPCHK(hipMemsetAsync(rp.p, 0, bytes, th->ctx->stream));
+    HIPCHK(hipStreamSynchronize(th->ctx->stream));
+    th->omega = std::move(om), th->rprev = std::move(rp);
+  }
+  th->dmg = D;
+  th->respond_dirty = true;
+  return FUS_OK;
 }
 
 int fus_thermal_boundary_info(fus_thermal* th, int64_t* nfixed, int64_t* nconvective)

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "thermal_response.hpp"
+
 namespace fus
 {
 
@@ -266,6 +268,76 @@ k_thermal_heat_harmonic(int64_t nvec, const T* __restrict__ mk, const double* __
   }
 }
 
+// ---- perfusion response and Arrhenius damage (fus_thermal_set_response, fus_thermal_set_damage; laws: thermal_response.hpp) ----
+// One launch after a step's last stage (several ranks: after the interface kernel; RKL2: after the fixed values are put
+// back), over all n_internal slots.  From the state the step ended in, T = t_base + (double) theta_{n+1} and D_{n+1}:
+//   MODE & 1 (response):  m_Weff = (T)((double) m_W * (P(T) * S(D)))       the perfusion plane the NEXT step's stages read
+//   MODE & 2 (damage):    Omega += dt2 * (r_prev + r(T)),  r_prev = r(T)   dt2 = dt / 2: the trapezoid rule over the step
+// every operation rounded by itself.  prime != 0 is the launch before the first step after the state, the response or the
+// boundary changed: m_Weff and r_prev are formed from the state as it stands, Omega and the old r_prev are not read.
+// The form of k_thermal_stage: a thread takes 16 bytes of every T vector (and the 2 or 4 doubles that belong to them), all
+// accesses 16-byte and non-temporal, a grid-stride loop, no LDS, no atomics.  The knot table and the scalars arrive by value
+// in the arguments; P selects its segment by comparisons against them, never through an index into memory.  m_Weff is zero
+// in the padding slots because m_W is; the padding slots of the double planes, like the dose plane's, hold values nobody
+// reads.  Every operand has the same bits on all sharers of an interface DOF, so the results do too, without an exchange.
+template <typename T>
+struct ThermalRespond
+{
+  const T* th;          // theta_{n+1}
+  const double* dose;   // D_{n+1} (response)
+  const T* mw;          // m_W (response)
+  T* mweff;             // m_Weff (response)
+  double* omega;        // Omega (damage)
+  double* rprev;        // r at the last state seen (damage)
+  ThermalResponse R;
+  double lnA, Ea, dt2, t_base;
+  int prime;
+};
+
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) k_thermal_response(int64_t nvec, const ThermalRespond<T> A)
+{
+#pragma clang fp contract(off)
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  typedef double D2 __attribute__((ext_vector_type(2)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    const TV th = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.th) + i);
+    TV mw, out;
+    if (MODE & 1)
+      mw = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A.mw) + i);
+#pragma unroll
+    for (int j = 0; j < VEC / 2; ++j)
+    {
+      const int64_t at = i * VEC + 2 * j;
+      const double T0 = A.t_base + (double)th[2 * j], T1 = A.t_base + (double)th[2 * j + 1];
+      if (MODE & 1)
+      {
+        const D2 d = __builtin_nontemporal_load(reinterpret_cast<const D2*>(A.dose + at));
+        const double phi0 = thermal_response_P(A.R, T0) * thermal_response_S(A.R, d[0]);
+        const double phi1 = thermal_response_P(A.R, T1) * thermal_response_S(A.R, d[1]);
+        out[2 * j] = (T)((double)mw[2 * j] * phi0), out[2 * j + 1] = (T)((double)mw[2 * j + 1] * phi1);
+      }
+      if (MODE & 2)
+      {
+        D2 rn;
+        rn[0] = thermal_damage_rate(A.lnA, A.Ea, T0), rn[1] = thermal_damage_rate(A.lnA, A.Ea, T1);
+        if (!A.prime)
+        {
+          const D2 ro = __builtin_nontemporal_load(reinterpret_cast<const D2*>(A.rprev + at));
+          D2 om = __builtin_nontemporal_load(reinterpret_cast<const D2*>(A.omega + at));
+          om[0] = om[0] + A.dt2 * (ro[0] + rn[0]), om[1] = om[1] + A.dt2 * (ro[1] + rn[1]);
+          __builtin_nontemporal_store(om, reinterpret_cast<D2*>(A.omega + at));
+        }
+        __builtin_nontemporal_store(rn, reinterpret_cast<D2*>(A.rprev + at));
+      }
+    }
+    if (MODE & 1)
+      __builtin_nontemporal_store(out, reinterpret_cast<TV*>(A.mweff) + i);
+  }
+}
+
 // q_coef = 2 alpha / (rho c) per cell, internal cell order (alpha: amplitude absorption, Np/m)
 template <typename T>
 __global__ void k_thermal_qcoef(int64_t n, const T* __restrict__ alpha, const T* __restrict__ rho, const T* __restrict__ c,
@@ -276,13 +348,14 @@ __global__ void k_thermal_qcoef(int64_t n, const T* __restrict__ alpha, const T*
     out[e] = T(2) * alpha[e] / (rho[e] * c[e]);
 }
 
-// Power iteration of fus_thermal_lambda_max: y = (K(k) x + m_W x) / m_C from b = K(-k) x
+// Power iteration of fus_thermal_lambda_max: y = (K(k) x + phi_max m_W x) / m_C from b = K(-k) x; phi_max bounds the
+// perfusion response from above (1 without one: the product with m_W is then exact)
 template <typename T>
 __global__ void k_thermal_power(int64_t n, const T* __restrict__ b, const T* __restrict__ x, const T* __restrict__ mw,
-                                const T* __restrict__ minv, T* __restrict__ y)
+                                T phi_max, const T* __restrict__ minv, T* __restrict__ y)
 {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = (mw[i] * x[i] - b[i]) * minv[i];
+    y[i] = ((phi_max * mw[i]) * x[i] - b[i]) * minv[i];
 }
 
 // ---- boundary conditions of the bioheat model (fus_thermal_set_boundary; entry lists: thermal_bc.hpp) ----

@@ -15,7 +15,7 @@ FUS_HOST, FUS_DEVICE = 0, 1
 FUS_LINEAR, FUS_LOSSY, FUS_WESTERVELT = 0, 1, 2
 FUS_U, FUS_V = 0, 1
 FUS_MON_MAX, FUS_MON_MIN, FUS_MON_MEAN, FUS_MON_RMS, FUS_MON_COS, FUS_MON_SIN = range(6)
-FUS_TH_RISE, FUS_TH_DOSE, FUS_TH_HEAT = 0, 1, 2
+FUS_TH_RISE, FUS_TH_DOSE, FUS_TH_HEAT, FUS_TH_DAMAGE, FUS_TH_PERFUSION = 0, 1, 2, 3, 4
 
 # every symbol include/fusmi.h declares
 SYMBOLS = [
@@ -35,6 +35,7 @@ SYMBOLS = [
     "fus_thermal_set_heat", "fus_thermal_set_heat_from_monitor", "fus_thermal_set_heat_from_harmonics",
     "fus_thermal_lambda_max", "fus_thermal_steps",
     "fus_thermal_steps_sts", "fus_thermal_stable_dt", "fus_thermal_set_boundary", "fus_thermal_boundary_info",
+    "fus_thermal_set_response", "fus_thermal_set_damage",
     "fus_group_thermal_finish", "fus_group_thermal_steps", "fus_group_thermal_lambda_max", "fus_group_thermal_stable_dt",
 ]
 

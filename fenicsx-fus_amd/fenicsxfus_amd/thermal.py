@@ -11,7 +11,9 @@ heat load comes from a nodal field (:meth:`set_heat`) or, without leaving the de
 model that shares the operator data (:meth:`set_heat_from`): ``Q = 2 alpha p_rms^2 / (rho c)``, or harmonic by harmonic
 with an absorption that grows with frequency.  Every face is
 insulating until :meth:`BioheatSpectralExplicit.set_boundary` holds it at a temperature (a cut face in tissue) or lets it
-exchange heat with a coolant (water-cooled skin).  The reference package has no thermal model; this module replaces
+exchange heat with a coolant (water-cooled skin).  The perfusion may follow the temperature and the dose
+(:meth:`BioheatSpectralExplicit.set_response`; :func:`perfusion_factor`), and the Arrhenius damage integral is accumulated
+beside the dose (:meth:`BioheatSpectralExplicit.set_damage`; :func:`arrhenius_rate`).  The reference package has no thermal model; this module replaces
 nothing there."""
 from __future__ import annotations
 
@@ -37,6 +39,38 @@ def cem43(temps, dt: float, t_base: float = 0.0):
         c = np.where(T >= 43.0, 1.0, 2.0)
         D = D + (dt / 60.0) * np.exp2(-(c * (43.0 - T)))
     return D
+
+
+GAS_CONSTANT = 8.314462618          # J/mol/K
+
+
+def perfusion_factor(T, D, temps=None, factors=None, dose_range=None):
+    """The perfusion response in numpy (fusmi.h "perfusion response and damage"): ``phi = P(T) * S(D)`` for temperatures
+    ``T`` in degrees C and doses ``D`` in CEM43 minutes, in double, in the order the kernel uses.  ``P`` is piecewise
+    linear through the knots ``(temps[j], factors[j])`` and constant outside them (1 without knots); ``S`` falls linearly
+    from 1 at ``dose_range[0]`` to 0 at ``dose_range[1]`` (1 without a range; equal ends: a step, 1 at the end itself)."""
+    T, D = np.asarray(T, dtype=np.float64), np.asarray(D, dtype=np.float64)
+    P = np.ones_like(T)
+    if temps is not None and len(temps):
+        t, f = np.asarray(temps, dtype=np.float64), np.asarray(factors, dtype=np.float64)
+        j = np.clip(np.searchsorted(t, T, side="right") - 1, 0, max(len(t) - 2, 0))
+        if len(t) > 1:
+            P = f[j] + (f[j + 1] - f[j]) * ((T - t[j]) / (t[j + 1] - t[j]))
+        P = np.where(T <= t[0], f[0], np.where(T >= t[-1], f[-1], P))
+    S = np.ones_like(D)
+    if dose_range is not None and dose_range[1] > 0:
+        lo, hi = float(dose_range[0]), float(dose_range[1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            S = np.where(D <= lo, 1.0, np.where(D >= hi, 0.0, (hi - D) / (hi - lo)))
+    return P * S
+
+
+def arrhenius_rate(T, A: float, Ea: float):
+    """The damage rate in numpy: ``exp(log(A) - Ea / (R (T + 273.15)))`` in 1/s for temperatures ``T`` in degrees C, ``A``
+    in 1/s, ``Ea`` in J/mol, R = 8.314462618, in double, in the order the kernel uses.  One step from ``T_old`` to
+    ``T_new`` adds ``(dt / 2) * (rate(T_old) + rate(T_new))`` to the damage integral."""
+    T = np.asarray(T, dtype=np.float64)
+    return np.exp(np.log(float(A)) - float(Ea) / (GAS_CONSTANT * (T + 273.15)))
 
 
 STS_MIN_STAGES, STS_MAX_STAGES = 2, 32
@@ -130,8 +164,12 @@ class BioheatSpectralExplicit:
         """Rise and dose to zero."""
         check(lib().fus_thermal_init(self.h))
 
-    def set_state(self, rise=None, dose=None):
-        """Set the temperature rise (K over ``t_base``) and / or the dose (minutes, float64), one value per DOF."""
+    def set_state(self, rise=None, dose=None, damage=None):
+        """Set the temperature rise (K over ``t_base``), the dose (minutes, float64) and / or the damage integral
+        (float64; :meth:`set_damage` must be on), one value per DOF."""
+        if damage is not None:
+            a = self._dofs(damage, "damage", np.float64)
+            check(lib().fus_thermal_set(self.h, C.c_int(_abi.FUS_TH_DAMAGE), ptr(a), C.c_int(_abi.FUS_HOST)))
         if rise is not None:
             a = self._dofs(rise, "rise")
             check(lib().fus_thermal_set(self.h, C.c_int(_abi.FUS_TH_RISE), ptr(a), C.c_int(_abi.FUS_HOST)))
@@ -236,10 +274,34 @@ class BioheatSpectralExplicit:
         check(lib().fus_thermal_boundary_info(self.h, C.byref(nf), C.byref(nc)))
         return nf.value, nc.value
 
+    def set_response(self, temps=None, factors=None, dose_range=None):
+        """Let the perfusion follow the temperature and the dose (:func:`perfusion_factor`): each step runs with
+        ``m_W * phi`` of the state it starts from.  ``temps`` / ``factors``: up to 8 knots, temperatures in degrees C
+        strictly ascending, factors >= 0; ``dose_range`` = ``(dose_lo, dose_hi)`` in CEM43 minutes, the shutdown of
+        coagulated tissue.  Replaces any response set before; all None clears it.  Call it before :meth:`stable_dt`: the
+        step rule then takes the largest factor."""
+        t = np.zeros(0) if temps is None else np.ascontiguousarray(temps, dtype=np.float64).ravel()
+        f = np.zeros(0) if factors is None else np.ascontiguousarray(factors, dtype=np.float64).ravel()
+        if len(t) != len(f):
+            raise _abi.FusError(f"set_response: {len(t)} temperatures but {len(f)} factors")
+        lo, hi = (0.0, 0.0) if dose_range is None else (float(dose_range[0]), float(dose_range[1]))
+        check(lib().fus_thermal_set_response(self.h, C.c_int(len(t)), ptr(t) if len(t) else None,
+                                             ptr(f) if len(f) else None, C.c_double(lo), C.c_double(hi)))
+
+    def clear_response(self):
+        """Back to the passive perfusion: steps then run exactly as on an object that never had a response."""
+        check(lib().fus_thermal_set_response(self.h, C.c_int(0), None, None, C.c_double(0.0), C.c_double(0.0)))
+
+    def set_damage(self, A: float, Ea: float = 0.0):
+        """Accumulate the Arrhenius damage integral (:func:`arrhenius_rate`; trapezoid rule per step) from now on: ``A``
+        in 1/s, ``Ea`` in J/mol.  ``A`` = 0 switches it off and frees its memory."""
+        check(lib().fus_thermal_set_damage(self.h, C.c_double(A), C.c_double(Ea)))
+
     def lambda_max(self, iters: int = 20) -> float:
         """Rayleigh quotient after ``iters`` power iterations: a lower bound of the largest eigenvalue of
-        ``m_C^-1 (K(k) + diag(m_W + m_H))`` (1/s) with the rows and columns of the fixed DOFs removed -- m_H the
-        convective faces' diagonal, zero without :meth:`set_boundary`."""
+        ``m_C^-1 (K(k) + diag(phi_max m_W + m_H))`` (1/s) with the rows and columns of the fixed DOFs removed -- m_H the
+        convective faces' diagonal, zero without :meth:`set_boundary`; phi_max the largest factor of
+        :meth:`set_response`, 1 without one."""
         out = C.c_double()
         check(lib().fus_thermal_lambda_max(self.h, C.c_int(iters), C.byref(out)))
         return out.value
@@ -287,6 +349,14 @@ class BioheatSpectralExplicit:
     def heat(self) -> Function:
         """The heat load vector ``h`` (W per DOF)."""
         return self._get(_abi.FUS_TH_HEAT, self.dtype)
+
+    def damage(self) -> Function:
+        """The Arrhenius damage integral Omega (float64); :meth:`set_damage` must be on."""
+        return self._get(_abi.FUS_TH_DAMAGE, np.float64)
+
+    def perfusion(self) -> Function:
+        """The perfusion plane the next step will use, ``m_W * phi`` (W/K per DOF): ``m_W`` itself without a response."""
+        return self._get(_abi.FUS_TH_PERFUSION, self.dtype)
 
     def close(self):
         """Frees the thermal object, and the operator data if this object created it."""

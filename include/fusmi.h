@@ -483,7 +483,8 @@ int fus_model_set_source_signals(fus_model* model, int64_t nchan, int64_t nsamp,
  *   fus_thermal_init     theta = 0 (fixed DOFs: their values), D = 0
  *   fus_thermal_set      which = FUS_TH_RISE: T[ndofs] (fixed DOFs take their values again); FUS_TH_DOSE: double[ndofs];
  *                        caller numbering, `space`
- *   fus_thermal_get      FUS_TH_RISE, FUS_TH_HEAT (= h): T[ndofs]; FUS_TH_DOSE: double[ndofs]
+ *   fus_thermal_get      FUS_TH_RISE, FUS_TH_HEAT (= h): T[ndofs]; FUS_TH_DOSE: double[ndofs]; FUS_TH_DAMAGE and
+ *                        FUS_TH_PERFUSION: "perfusion response and damage" below
  *   fus_thermal_set_heat q: T[ndofs], q_coef: T[ncells] or NULL (= 1), both in `space`; q == NULL: h = 0
  *   fus_thermal_set_heat_from_monitor   h from the field monitor of a wave model on the SAME fus_op, without leaving
  *                        the device: q = Q / n from the monitor's sum-of-squares plane and sample count, formed in
@@ -569,9 +570,54 @@ int fus_model_set_source_signals(fus_model* model, int64_t nchan, int64_t nsamp,
  * sum_k m_k(part) .* a_k rounded to T, are summed in one ordered exchange (not K weights), and all sharers end with the
  * same bits.  Under RCCL the call is collective and exchanges at once; in an in-process group the part waits for
  * fus_group_thermal_finish like any heat load (on every member or none, and of the same kind on all of them);
- * fus_thermal_set_heat(q = NULL) drops it. */
+ * fus_thermal_set_heat(q = NULL) drops it.
+ * Perfusion response and damage (fus_thermal_set_response, fus_thermal_set_damage).  Blood flow rises several-fold under
+ * mild heating and stops for good where the tissue is coagulated; fus_thermal_set_response lets the perfusion term follow
+ * the temperature and the dose, one law per thermal object (tissue differences stay in the per-cell W).  With
+ * T = t_base + (double) theta and the dose D of a DOF, in double for both scalar types, every operation rounded by itself:
+ *   P(T)   1 if nknots == 0; else factor[0] for T <= temp[0], factor[n-1] for T >= temp[n-1], and between them, with j
+ *          the largest index with temp[j] <= T:
+ *            factor[j] + (factor[j+1] - factor[j]) * ((T - temp[j]) / (temp[j+1] - temp[j]))
+ *   S(D)   1 if dose_hi <= 0 (no shutdown); else 1 for D <= dose_lo, 0 for D >= dose_hi,
+ *          (dose_hi - D) / (dose_hi - dose_lo) between them; dose_lo == dose_hi > 0 is a step (1 at D == dose_lo)
+ *   phi = P * S,      m_Weff = (T)((double) m_W * phi)
+ * phi is taken from the state at the START of a step, (theta_n, D_n), and held through all stages of that step, for RK4
+ * and for every RKL2 stage count alike: within a step the operator is the linear, symmetric one both step rules assume,
+ * and f reads m_Weff where it read m_W.
+ *   nknots 0..8; temp strictly ascending and finite, degrees C; factor finite and >= 0; 0 <= dose_lo <= dose_hi (finite),
+ *   or dose_hi <= 0.  Anything else is FUS_ERR_ARG, and the response stays as it was.  nknots == 0 with dose_hi <= 0
+ *   clears the response.  Legal before or after fus_thermal_init and between steps; the state is kept.  On an object
+ *   without perfusion the call is accepted and changes no result.
+ * Step rule: fus_thermal_lambda_max and fus_thermal_stable_dt (and the group forms) then work on
+ * m_C^-1 (K(k) + diag(phi_max m_W + m_H)), phi_max = max_j factor[j] (1 without knots).  The difference to the operator of
+ * any phi in force, diag((phi_max - phi) m_W), is a non-negative diagonal, and adding one cannot lower an eigenvalue of the
+ * symmetric pencil: the quotient's lambda_max bounds that of every state from above, so the step taken from it is stable
+ * throughout.  Like fus_thermal_set_boundary, fus_thermal_set_response must therefore precede fus_thermal_stable_dt.
+ * Damage: fus_thermal_set_damage(A, Ea) switches on the Arrhenius integral Omega, double[ndofs] for both scalar types,
+ * zeroed by the call that switches it on and by fus_thermal_init.  A in 1/s, Ea in J/mol, both positive and finite (else
+ * FUS_ERR_ARG); A == 0 switches the damage off and frees its memory; new constants on a running integral keep its value.
+ * After every completed step of EITHER scheme, from theta_old to theta_new, in double, every operation rounded by itself:
+ *   r(T) = exp(lnA - Ea / (R * (T + 273.15))),   R = 8.314462618,   lnA = log(A) taken once on the host
+ *   Omega += (dt / 2) * (r(T_old) + r(T_new))                        (trapezoid rule)
+ * Fixed DOFs accumulate damage from their fixed temperature, as the dose does.
+ *   fus_thermal_get / _set   FUS_TH_DAMAGE: double[ndofs], FUS_ERR_STATE while the damage is off
+ *   fus_thermal_get          FUS_TH_PERFUSION: T[ndofs], read only: the plane m_Weff the next step will use -- m_W itself
+ *                            while no response is set, zeros without perfusion
+ * Cost: while neither is set a step enqueues exactly the launches of an object that never had them, with the same
+ * arguments (the stage kernels keep reading m_W).  With either set, a step gains ONE streaming launch (profile name
+ * "thermal_response") after its last stage -- on several ranks after the interface kernel, on the RKL2 path after
+ * "thermal_fix".  It reads theta_{n+1}, D_{n+1} and m_W, and for the damage Omega and a stored double plane with
+ * r(T_{n+1}) of the step before; it writes m_Weff for the next step, Omega and that plane: the stage kernels only get
+ * another pointer.  The knot table travels in the kernel arguments.  A steps call (or a read of FUS_TH_PERFUSION) starts
+ * with one more such launch when fus_thermal_init, _set, _set_boundary, _set_response or _set_damage (or a
+ * fus_group_thermal_finish that had work) came since the last step: it forms m_Weff and the stored rate from the state as
+ * it stands and leaves Omega alone.
+ * Several ranks: every operand of phi and r (the states, D, the summed m_W) has the same bits on all sharers of a DOF, so
+ * the launch covers all of a rank's slots without an exchange and the sharers stay identical; under RCCL nothing becomes
+ * collective.  fus_group_thermal_steps, _lambda_max and _stable_dt check before anything is enqueued that all members
+ * carry the same response and damage parameters (else FUS_ERR_STATE). */
 typedef struct fus_thermal fus_thermal;
-enum { FUS_TH_RISE = 0, FUS_TH_DOSE = 1, FUS_TH_HEAT = 2 };
+enum { FUS_TH_RISE = 0, FUS_TH_DOSE = 1, FUS_TH_HEAT = 2, FUS_TH_DAMAGE = 3, FUS_TH_PERFUSION = 4 };
 int fus_thermal_create(fus_ctx* ctx, fus_op* op, const void* conductivity, const void* rho_c,
                        const void* perfusion /* NULL = 0 */, double t_base, fus_thermal** thermal);
 int fus_thermal_destroy(fus_thermal* thermal);
@@ -592,6 +638,9 @@ int fus_thermal_set_boundary(fus_thermal* thermal, const uint8_t* fixed /* [ndof
                              const void* fixed_rise /* T[ndofs], read where fixed */,
                              const void* conv_diag /* T[ndofs] = m_H >= 0 */, const void* conv_rise /* T[ndofs] */);
 int fus_thermal_boundary_info(fus_thermal* thermal, int64_t* nfixed, int64_t* nconvective);
+int fus_thermal_set_response(fus_thermal* thermal, int nknots /* 0..8 */, const double* temp /* [nknots], degrees C */,
+                             const double* factor /* [nknots], >= 0 */, double dose_lo, double dose_hi /* <= 0: no shutdown */);
+int fus_thermal_set_damage(fus_thermal* thermal, double A /* 1/s; 0: off */, double Ea /* J/mol */);
 /* the members of an in-process group, one thermal object per rank, in any order */
 int fus_group_thermal_finish(fus_thermal** thermals, int n);
 int fus_group_thermal_steps(fus_thermal** thermals, int n, double dt, int64_t nsteps, double heat_scale,
@@ -634,7 +683,8 @@ int fus_model_stage_end(fus_model* model, int stage, double t, double dt);
  * "thermal" (bioheat stage update; its operator passes count under "stiffness" and "shared"), "thermal_sts" (the
  * same for a super-time-stepping stage), "thermal_bc" (convective surface term, once per operator application of a
  * bioheat object with convective DOFs), "thermal_fix" (writes of the fixed values), "thermal_if" (bioheat stage update of
- * the interface DOFs on several ranks; the pack of their totals counts under "halo").  total_ms/count accumulate since the last enable.
+ * the interface DOFs on several ranks; the pack of their totals counts under "halo"), "thermal_response" (perfusion
+ * response and damage, once per step of a bioheat object that has either).  total_ms/count accumulate since the last enable.
  * on = 1: every kernel; on = 2: only the block operator kernel ("stiffness", and "stiffness_if" when
  * the interface blocks are launched separately) -- an event record drains the queue between two
  * kernels, so timed runs use 2 (bench.py) and take the full breakdown in a separate pass.  Option

@@ -413,7 +413,7 @@ public:
   {
     check(fus_thermal_set_heat_from_harmonics(h_, model.handle(), nharm, absorption));
   }
-  // of m_C^-1 (K(k) + diag(m_W + m_H)) with the fixed DOFs removed (the boundary in force)
+  // of m_C^-1 (K(k) + diag(phi_max m_W + m_H)) with the fixed DOFs removed (the boundary and the response in force)
   double lambda_max(int iters = 20) const
   {
     double l = 0;
@@ -448,9 +448,25 @@ public:
     check(fus_thermal_boundary_info(h_, &nf, &nc));
     return {nf, nc};
   }
+  // Perfusion response (fusmi.h "bioheat", perfusion response and damage): each step runs with m_W phi of the state it
+  // starts from, phi = P(T) S(D) -- P piecewise linear through up to 8 knots (temp strictly ascending, degrees C;
+  // factor >= 0), S falling from 1 at dose_lo to 0 at dose_hi CEM43 minutes (dose_hi <= 0: no shutdown).  Call it before
+  // stable_dt, which then takes the largest factor.  clear_response: the passive perfusion again.
+  void set_response(const std::vector<double>& temp, const std::vector<double>& factor, double dose_lo = 0.0,
+                    double dose_hi = 0.0)
+  {
+    if (temp.size() != factor.size())
+      throw Error(FUS_ERR_ARG, "set_response: temp and factor differ in length");
+    check(fus_thermal_set_response(h_, (int)temp.size(), temp.data(), factor.data(), dose_lo, dose_hi));
+  }
+  void clear_response() { check(fus_thermal_set_response(h_, 0, nullptr, nullptr, 0.0, 0.0)); }
+  // Arrhenius damage integral beside the dose, trapezoid rule per step: A in 1/s, Ea in J/mol; A = 0 switches it off
+  void set_damage(double A, double Ea) { check(fus_thermal_set_damage(h_, A, Ea)); }
   std::vector<T> rise() const { return get<T>(FUS_TH_RISE); }
   std::vector<T> heat() const { return get<T>(FUS_TH_HEAT); }
   std::vector<double> dose() const { return get<double>(FUS_TH_DOSE); }  // CEM43, minutes
+  std::vector<double> damage() const { return get<double>(FUS_TH_DAMAGE); }   // Omega; set_damage must be on
+  std::vector<T> perfusion() const { return get<T>(FUS_TH_PERFUSION); }       // m_W phi as the next step will use it
   fus_thermal* handle() const { return h_; }
 
 private:
