@@ -26,12 +26,25 @@ static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x
     K.Dk.w[i] = (T)op->wts[i], K.Dk.x[i] = (T)op->nodes[i];
   // the attribute is per device: one bit per device and instantiation (set again harmlessly if two
   // threads race on the first launch)
+  // WALK = 1, the kernel with the block loop, runs where a launch can have fewer workgroups than blocks (option
+  // "walk", below); every other launch of a per-cell geometry kernel runs the straight-line kernel WALK = 0
+  constexpr bool CAN_WALK = GEOM != GEOM_STREAM && TD == 3;
+  // The streamed-geometry kernels (quadrilaterals among them) keep the kernel with the block loop for every launch:
+  // the straight-line form measured 0.45 % slower there in every round (profiles/block_overhead.md section 6)
+#ifdef FUS_PROBE_WALK_ALWAYS   // developer probe (A/B of the straight-line kernel): every launch runs the kernel with the block loop
+  constexpr int W0 = 1;
+#else
+  constexpr int W0 = CAN_WALK ? 0 : 1;
+#endif
+  const void* const k_straight = reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK, W0>);
+  const void* const k_walking = reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK, CAN_WALK ? 1 : W0>);
   static std::atomic<uint64_t> attr_set{0};
   const uint64_t dev_bit = 1ull << (op->ctx->device & 63);
   if (!(attr_set.load(std::memory_order_relaxed) & dev_bit))
   {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(k_straight, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (k_walking != k_straight)
+      HIPCHK(hipFuncSetAttribute(k_walking, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
   }
   K.A = op->A;
@@ -59,7 +72,7 @@ static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x
   // hardware's own dispatch of a fresh workgroup into a freed slot overlaps the phases of different
   // blocks better than the walking workgroup's software pipeline does.
   int grid = blk_count;
-  if (GEOM != GEOM_STREAM && TD == 3 && op->ctx->walk != 0)
+  if (CAN_WALK && op->ctx->walk != 0)
   {
     int per_cu = op->ctx->walk;
     if (per_cu < 0)  // as many workgroups per CU as are resident at once, where each then has >= 4 blocks to walk
@@ -76,8 +89,7 @@ static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x
         {
           int nb = 0;
           HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &nb, reinterpret_cast<const void*>(&k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>), 64 * op->L.waves,
-              op->lds_bytes));
+              &nb, k_walking, 64 * op->L.waves, op->lds_bytes));
           it = occ_cache.emplace(key, std::max(nb, 1)).first;
         }
         occ = it->second;
@@ -87,8 +99,12 @@ static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x
     if (per_cu > 0)
       grid = std::min(blk_count, per_cu * op->ctx->num_cus);
   }
-  hipLaunchKernelGGL((k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK>), dim3(grid),
-                     dim3(64 * op->L.waves), op->lds_bytes, op->ctx->stream, K);
+  if (CAN_WALK && grid < blk_count)
+    hipLaunchKernelGGL((k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK, CAN_WALK ? 1 : W0>), dim3(grid),
+                       dim3(64 * op->L.waves), op->lds_bytes, op->ctx->stream, K);
+  else
+    hipLaunchKernelGGL((k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK, W0>), dim3(grid),
+                       dim3(64 * op->L.waves), op->lds_bytes, op->ctx->stream, K);
   HIPCHK(hipGetLastError());
   return FUS_OK;
 }

@@ -2374,6 +2374,44 @@ __device__ __forceinline__ V stage_update_dof(int64_t s, V acc, const T* __restr
 }
 #undef FUS_STAGE_VECTORS
 
+// Range-checked access to ONE block's range of an array (k_block_op's prologue and stage epilogue): a raw buffer
+// descriptor built from wave-uniform scalars -- base = array + the block's offset, `bytes` = the length of the block's range, never a whole
+// vector (a vector may be longer than the 32-bit byte count of a descriptor) -- and the lane's byte offset within the
+// range in a 32-bit register.  The hardware's range check takes the place of a compare, an exec-mask branch and a
+// zero-fill around every access: a load past `bytes` touches no memory and returns 0.  bytes <= 0: every lane is out
+// of range.  The loads of one round then stand in one basic block, where the compiler counts them (vmcnt) instead of
+// draining the queue.
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t range_rsrc(const T* base, int bytes)
+{
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, bytes > 0 ? bytes : 0, 0x00020000);
+}
+// the V (4, 8 or 16 bytes) at byte offset `off` of the range; NT: non-temporal, like __builtin_nontemporal_load / _store
+constexpr int RANGE_NT = 2;   // the "nt" bit of a buffer access's cache policy
+template <typename V, int NT = 0>
+__device__ __forceinline__ V range_load(__amdgpu_buffer_rsrc_t r, int off)
+{
+  static_assert(sizeof(V) == 4 || sizeof(V) == 8 || sizeof(V) == 16, "one buffer load");
+  if constexpr (sizeof(V) == 4)
+    return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, NT ? RANGE_NT : 0));
+  else if constexpr (sizeof(V) == 8)
+    return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, NT ? RANGE_NT : 0));
+  else
+    return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, NT ? RANGE_NT : 0));
+}
+// a store past the range is dropped
+template <typename V, int NT = 0>
+__device__ __forceinline__ void range_store(V v, __amdgpu_buffer_rsrc_t r, int off)
+{
+  static_assert(sizeof(V) == 8 || sizeof(V) == 16, "one buffer store");
+  typedef unsigned int B2 __attribute__((ext_vector_type(2)));
+  typedef unsigned int B4 __attribute__((ext_vector_type(4)));
+  if constexpr (sizeof(V) == 8)
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(B2, v), r, off, 0, NT ? RANGE_NT : 0);
+  else
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(B4, v), r, off, 0, NT ? RANGE_NT : 0);
+}
+
 // The block kernel's only argument (read in the kernel through the kernarg segment pointer, see FUS_KARGS).
 template <typename T, int N>
 struct KArgs
@@ -2418,7 +2456,10 @@ __device__ __forceinline__ void load_stage_args(const KArgs<T, N> __attribute__(
 // no geometry registers -- are compiled for FUS_TRI_WAVES(P) waves per SIMD with the lane's
 // derivative-table rows read from LDS where used.
 // TD = 2: the same block machinery for quadrilateral elements (Nd = N^2, GEOM_STREAM only).
-template <typename T, int P, int OP, int ATOMIC, int STAGE, int NF, int GEOM, int TD = 3, int MF = 0, int PK = 0>
+// WALK = 0: the launch has one workgroup per block (the default).  The kernel is then straight-line code for one
+// block: no block loop, no second phase, the block's record and the kernel arguments read once.  WALK = 1: a
+// workgroup walks several blocks (option "walk": fewer workgroups than blocks), with everything the loop needs.
+template <typename T, int P, int OP, int ATOMIC, int STAGE, int NF, int GEOM, int TD = 3, int MF = 0, int PK = 0, int WALK = 1>
 __global__ void __launch_bounds__((P <= 4) ? 512 : FUS_MID_THREADS, (P >= 8) ? FUS_HI_WAVES : (P <= 4 && is_aff(GEOM))
                                                             ? 4
                                                             : ((GEOM == GEOM_TRILINEAR || (is_aff(GEOM) && P <= 6)) ? FUS_TRI_WAVES_T(T, P) : (FUS_PF1(T, P, OP, ATOMIC, GEOM, TD) ? 2 : 1)))
@@ -2444,14 +2485,17 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
                 "packed path: fp32 stiffness, degrees 5-7, per-cell geometry, LDS-atomic accumulation");
   constexpr int EPS = PK ? 2 : 1;   // elements per lane group and trip
 
-  // Kernel arguments are read from the kernarg segment where they are used, through a pointer that is
+  // Kernel arguments are read from the kernarg segment where they are used.  WALK = 1: through a pointer that is
   // made opaque again at the start of every phase (FUS_KARGS): a workgroup that walks several blocks
   // would otherwise keep all ~150 scalar registers' worth of arguments live around the block loop and
-  // spill them.
+  // spill them.  WALK = 0 has no loop to keep them live around: the pointer stays transparent, and an argument
+  // or a field of the block's record that several phases use is read once.
   typedef const KArgs<T, N> __attribute__((address_space(4))) * KP;
+  constexpr bool OPAQUE = WALK != 0;
 #define FUS_KARGS(q)                                                                               \
   KP q = (KP)__builtin_amdgcn_kernarg_segment_ptr();                             \
-  asm volatile("" : "+s"(q))
+  if constexpr (OPAQUE)                                                                            \
+    asm volatile("" : "+s"(q))
   constexpr int GCS = geom_cell_stride(GEOM);               // per-cell geometry numbers (7 / 21 / 0)
   // FUS_ACC: the block accumulator y_l is fp64 for every scalar type.  On gfx950 the LDS atomic ds_add_f32 is
   // an order of magnitude slower than ds_add_f64 / ds_add_u32 / a plain store (fp32 p=6: a third of the kernel,
@@ -2481,11 +2525,12 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       (void)ldm_l, (void)rt_l, (void)slots
 
   const int tid0 = threadIdx.x, nthr = blockDim.x;
-  // the thread index, opaque per phase like the lane coordinates (FUS_TID): address arithmetic of one phase
+  // the thread index, opaque per phase like the lane coordinates (FUS_TID; WALK = 1): address arithmetic of one phase
   // must not be hoisted out of the block loop and stay live through the others
 #define FUS_TID()                                                                                  \
   int tid = tid0;                                                                                  \
-  asm volatile("" : "+v"(tid))
+  if constexpr (OPAQUE)                                                                            \
+    asm volatile("" : "+v"(tid))
   // lane coordinates: recomputed per block from a value the compiler cannot trace (FUS_LANE_COORDS), so that
   // the address arithmetic of the element trips is not hoisted out of the block loop of a walking
   // workgroup and kept live (and spilled) across its prologue / epilogue phases
@@ -2526,6 +2571,24 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   };
   typedef T V2 __attribute__((ext_vector_type(2)));
   typedef uint32_t U4 __attribute__((ext_vector_type(4)));
+  // Range-checked accesses (range_rsrc) in the prologue's first batch and in the stage epilogue's interior passes: the
+  // fp64 per-cell geometry kernels of the degrees <= 4, where they were measured (profiles/block_overhead.md) and
+  // where the descriptors' scalar registers fit.  Elsewhere they cost registers the kernels do not have: the
+  // streamed-geometry kernels sit at the register limit with their two sets of geometry registers (eight of the
+  // degree-4 fp64 ones went into scratch), and so did the fp32 trilinear kernels of degree 5 and one of degree 4,
+  // compiled for four waves per SIMD.  Those keep the guarded form: a compare, an exec-mask branch and a zero-fill
+  // per access.
+  constexpr bool RANGED_FITS = GEOM != GEOM_STREAM && sizeof(T) == 8 && P <= 4;
+#ifdef FUS_PROBE_GUARDED_LOADS   // developer probe (A/B of the range-checked prologue): the guarded form everywhere
+  constexpr bool RANGED_PROLOGUE = false;
+#else
+  constexpr bool RANGED_PROLOGUE = RANGED_FITS;
+#endif
+#ifdef FUS_PROBE_GUARDED_EPILOGUE   // developer probe (A/B of the range-checked epilogue)
+  constexpr bool RANGED_EPILOGUE = false;
+#else
+  constexpr bool RANGED_EPILOGUE = RANGED_FITS;
+#endif
   // per thread: interior 16-B vectors, shared dofs, dofmap 16-B vectors of the first batch (what a block
   // of the default size needs; larger blocks finish in the plain loops of p_commit).  Kept small: these
   // registers are live across the epilogue of the previous block when a workgroup walks several blocks.
@@ -2551,9 +2614,20 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     FUS_TID();
     const int nsh = M.nloc - M.nint;
     const int32_t* gix = q->A.sh_gidx + M.sh_off;
+    if constexpr (!RANGED_PROLOGUE)
+    {
 #pragma unroll
-    for (int u = 0; u < US; ++u)
-      gi[u] = (enable && tid + u * nthr < nsh) ? gix[tid + u * nthr] : -1;
+      for (int u = 0; u < US; ++u)
+        gi[u] = (enable && tid + u * nthr < nsh) ? gix[tid + u * nthr] : -1;
+    }
+    else
+    {
+      // (past the block's list: index 0, see p_load)
+      const __amdgpu_buffer_rsrc_t rg = range_rsrc(gix, enable ? nsh * 4 : 0);
+#pragma unroll
+      for (int u = 0; u < US; ++u)
+        gi[u] = range_load<int>(rg, (tid + u * nthr) * 4);
+    }
   };
   auto p_load = [&](KP q, const Meta& M, PLoad& L, bool with_tables, bool enable, const int (&gi)[US])
       __attribute__((always_inline))
@@ -2574,6 +2648,41 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     const int n16 = (sh.nelem * Nd * 2 + 15) >> 4;  // ldm_off is a multiple of 8 entries
     const U4* lsrc = reinterpret_cast<const U4*>(q->A.ldm + sh.ldm_off);
     const int ngc = sh.nelem * GCS;
+    if constexpr (RANGED_PROLOGUE)
+    {
+      // round trip 1: range-checked loads (range_rsrc), one descriptor per array and block; no branch between them, so
+      // that the gather below waits for the indices alone (they left first, in p_idx) and not for the whole round
+      constexpr int TB = (int)sizeof(T), VB = (int)sizeof(V2);
+      const __amdgpu_buffer_rsrc_t rx = range_rsrc(x + M.int_off, enable ? nvec * VB : 0);
+      const __amdgpu_buffer_rsrc_t rx2 = range_rsrc(x2 + M.int_off, (NF == 2 && enable) ? nvec * VB : 0);
+#pragma unroll
+      for (int u = 0; u < UI; ++u)
+      {
+        L.xi[u] = range_load<V2>(rx, (tid + u * nthr) * VB);
+        L.xi2[u] = (NF == 2) ? range_load<V2>(rx2, (tid + u * nthr) * VB) : V2(T(0));
+      }
+      const __amdgpu_buffer_rsrc_t rl = range_rsrc(q->A.ldm + sh.ldm_off, enable ? n16 * 16 : 0);
+#pragma unroll
+      for (int u = 0; u < UL; ++u)
+        L.lq[u] = range_load<U4>(rl, (tid + u * nthr) * 16);
+      L.cfv = range_load<T>(range_rsrc(coef + M.elem_off, enable ? sh.nelem * TB : 0), tid * TB);
+      L.cf2v = (NF == 2) ? range_load<T>(range_rsrc(coef2 + M.elem_off, enable ? sh.nelem * TB : 0), tid * TB) : T(0);
+      const __amdgpu_buffer_rsrc_t rgc = range_rsrc(geo + (int64_t)M.elem_off * GCS, (GCS && enable) ? ngc * TB : 0);
+      L.gcv = GCS ? range_load<T>(rgc, tid * TB) : T(0);
+      L.gcv2 = (GCS > 7) ? range_load<T>(rgc, (tid + nthr) * TB) : T(0);
+      // derivative table, 1-D weights, 1-D points
+      L.dgv = range_load<T>(range_rsrc(Dg, (with_tables && enable) ? (N2 + 2 * N) * TB : 0), tid * TB);
+      // the shared dofs' values (their indices came with p_idx: 0 past the block's list, whose value p_commit leaves alone)
+#pragma unroll
+      for (int u = 0; u < US; ++u)
+      {
+        L.xs[u] = x[gi[u]];
+        L.xs2[u] = (NF == 2) ? x2[gi[u]] : T(0);
+      }
+      L.xtail = (enable && tid == 0 && (sh.nint & 1)) ? x[M.int_off + sh.nint - 1] : T(0);
+      L.xtail2 = (NF == 2 && enable && tid == 0 && (sh.nint & 1)) ? x2[M.int_off + sh.nint - 1] : T(0);
+      return;
+    }
     // round trip 1
     // (every field is assigned unconditionally: a register that is only written under a condition
     // would have to stay live across the element trips of a walking workgroup)
@@ -2784,21 +2893,43 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     elem_fetch<T, N, OP, GEOM, TD>(inA, e0, q->geo, Mm.elem_off, p);
   };
   PLoad L;
+  // WALK = 0 (the kernels of RANGED_FITS, where it was measured): what the prologue's loads are addressed with is
+  // requested in two batches of scalar loads at kernel entry -- the arguments, then the block's record -- instead of
+  // one by one where each is first used, every one behind a wait of its own
+#ifndef FUS_PROBE_ARGS_LATE   // developer probe (A/B of the entry batches): every scalar load where the compiler puts it
+  if constexpr (!WALK && RANGED_FITS)
+    asm volatile("" ::"s"(q0->A.blk_rec), "s"(q0->A.sh_gidx), "s"(q0->A.ldm), "s"(q0->A.waves), "s"(q0->x), "s"(q0->coef),
+                 "s"(q0->geo), "s"(q0->Dg));
+#endif
+  const Meta M0 = meta_of(q0, blk);
+#ifndef FUS_PROBE_ARGS_LATE
+  if constexpr (!WALK && RANGED_FITS)
+    asm volatile("" ::"s"(M0.elem_off), "s"(M0.int_off), "s"(M0.sh_off), "s"(M0.nelem), "s"(M0.nloc), "s"(M0.nint),
+                 "s"(M0.ldm_off));
+#endif
+  // the record of block bk in a later phase: read again by a walking workgroup (nothing of it is carried around the
+  // block loop), the one read at kernel entry otherwise
+  auto meta_at = [&](KP q, int bk) -> Meta
   {
-    const Meta M0 = meta_of(q0, blk);
+    if constexpr (WALK)
+      return meta_of(q, bk);
+    else
+      return M0;
+  };
+  {
     first_fetch(q0, M0);
     int gi0[US];
     p_idx(q0, M0, true, gi0);
     p_load(q0, M0, L, true, true, gi0);
   }
   bool first = true;
-  for (;;)
+  for (;;)   // WALK = 0: left after one block
   {
   // ---- phase 1: this block's staged data -> LDS, then the element trips ----
   FUS_KARGS(qc);
   FUS_PHASE_LDS(qc);
   FUS_LANE_COORDS(qc);
-  const Meta M = meta_of(qc, blk);
+  const Meta M = meta_at(qc, blk);
   const Meta& sh = M;
   const int elem_off = M.elem_off;
   // element of this lane group in trip r: conflict-free round table (deterministic mode) or simply
@@ -2829,7 +2960,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   // the next block of this workgroup: its shared-dof indices are requested now and ride through the trips
   // (degrees <= 4: a few registers), so that all of its prologue loads are independent in phase 2
   const int blk_next = blk + blk_stride;
-  const bool has_next = blk_next < blk_end;
+  const bool has_next = WALK && blk_next < blk_end;
   // (measured: requesting them here costs more than it saves -- the barrier ahead of the trips waits for
   // them, 0.2525 -> 0.2620 ms at config 2 -- so the indices are read in phase 2)
   constexpr bool IDX_EARLY = false;
@@ -2959,7 +3090,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   FUS_KARGS(qe);
   FUS_PHASE_LDS(qe);
   FUS_TID();
-  const Meta M = meta_of(qe, blk);
+  const Meta M = meta_at(qe, blk);
   const Meta& sh = M;
   const int int_off = M.int_off;
   const int64_t sh_off = M.sh_off;
@@ -3013,8 +3144,14 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       // developer probe (wrong results): the stage update's operands cost no memory round trip
       auto ld = [&](const T* ptr) -> V2 { return E.on ? V2(T(1)) + V2(T((uintptr_t)ptr & 7)) : V2(T(0)); };
 #else
+      // range-checked (range_rsrc): the block's interior range of the vector, 0 past its end
       auto ld = [&](const T* ptr) -> V2
-      { return E.on ? __builtin_nontemporal_load(reinterpret_cast<const V2*>(ptr + E.o)) : V2(T(0)); };
+      {
+        if constexpr (RANGED_EPILOGUE)
+          return range_load<V2, 1>(range_rsrc(ptr + int_off, nvec * (int)sizeof(V2)), E.i * (int)sizeof(V2));
+        else
+          return E.on ? __builtin_nontemporal_load(reinterpret_cast<const V2*>(ptr + E.o)) : V2(T(0));
+      };
 #endif
       constexpr bool WV = NF == 2;   // Westervelt operands possible (S.mn1 decides at run time)
       if (STAGE == 0)
@@ -3051,7 +3188,13 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     {
       if (!E.on)
         return;
-      auto st = [&](T* ptr, V2 val) { __builtin_nontemporal_store(val, reinterpret_cast<V2*>(ptr + E.o)); };
+      auto st = [&](T* ptr, V2 val)
+      {
+        if constexpr (RANGED_EPILOGUE)
+          range_store<V2, 1>(val, range_rsrc(ptr + int_off, nvec * (int)sizeof(V2)), E.i * (int)sizeof(V2));
+        else
+          __builtin_nontemporal_store(val, reinterpret_cast<V2*>(ptr + E.o));
+      };
       V2 kv;
       if (NF == 2 && S.mn1)
       {
@@ -3116,11 +3259,14 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   __syncthreads();   // every element of the block has been accumulated
   FUS_STAMP(blk, 2);
 
-  // ---- phase 2: the next block of this workgroup -- its prologue loads travel while this block is
+  // ---- phase 2 (WALK = 1): the next block of this workgroup -- its prologue loads travel while this block is
   // written out ----
+  if constexpr (WALK)
   {
     // (always executed, with every load predicated on has_next: the staged registers are then defined on
-    // every path and not live across the trips)
+    // every path and not live across the trips.  The range-checked form predicates through the byte count of its
+    // descriptors -- 0 without a next block -- and its gather then reads x[0] (and x2[0]) in every lane: the operator's
+    // input vectors exist and are not empty whenever the kernel runs, and p_commit stores none of those values)
     FUS_KARGS(qn);
     Meta Mn{};
     if (has_next)
@@ -3200,7 +3346,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     partial[pp[k]] = (T)y_l[sh.nint + k];
   }
   FUS_TRACE_END(blk);
-  if (!has_next)
+  if (!WALK || !has_next)
     break;
   __syncthreads();  // every wave has read what it needs of this block's x_l / y_l
   blk = blk_next;

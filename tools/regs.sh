@@ -9,8 +9,9 @@ s=open('/tmp/regchk/p.s').read()
 for m in re.finditer(r'\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel', s, re.S):
     name,body=m.group(1),m.group(2)
     t=re.search(r'k_block_opI(\w)Li(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d)E',name)
+    w=re.search(r'ELi(\d)ELi(\d)ELi([01])EEEv',name)   # ... MF, PK, WALK
     if not t or t.group(7)!=sys.argv[1]: continue
     v=re.search(r'\.amdhsa_next_free_vgpr (\d+)',body).group(1)
     sp=re.search(r'\.amdhsa_private_segment_fixed_size (\d+)',body).group(1)
-    print('T=%s P=%s OP=%s ATOMIC=%s STAGE=%s NF=%s GEOM=%s TD=%s'%t.groups(),'vgpr',v,'scratch',sp)
+    print('T=%s P=%s OP=%s ATOMIC=%s STAGE=%s NF=%s GEOM=%s TD=%s'%t.groups(),'WALK=%s'%(w.group(3) if w else '?'),'vgpr',v,'scratch',sp)
 PY
