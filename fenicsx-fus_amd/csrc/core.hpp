@@ -158,6 +158,18 @@ struct FUS_HIDDEN ModelMonitor
   double t_first = 0.0, t_last = 0.0;
 };
 
+// relaxation absorption (fus_model_set_relaxation): nrelax processes, per process one memory variable z_nu and one
+// per-DOF strength A_nu, planes of n_internal T in one allocation each.  den: the lumped M(1/(rho c^2)) 1 kept while the
+// sums over the sharers of an in-process group are pending (fus_group_relaxation_finish divides by it and frees it).
+struct FUS_HIDDEN ModelRelax
+{
+  int nrelax = 0;
+  double omega[4] = {0, 0, 0, 0};   // angular relaxation frequencies, 1/s
+  DevBuf z, A;                      // T[nrelax][n_internal]
+  DevBuf den;                       // T[n_internal], only while pending
+  bool pending = false;
+};
+
 // Of the wave model the bioheat unit reads what its two heat-load calls need: op, d_rho0, d_c0 and the monitor's
 // mon.d_mon, mon.n, mon.nharm, mon.every, mon.which.
 struct fus_model
@@ -187,6 +199,8 @@ struct fus_model
   ModelSource src;
   ModelReceivers rc;
   ModelMonitor mon;
+  ModelRelax rx;
+  void* mcoef = nullptr;   // the mass coefficient 1/(rho c^2), internal cell order (the setup's; in allocs)
   // c0 and rho0 as fus_model_create was given them, internal cell order: fus_thermal_set_heat_from_monitor forms
   // q_coef = 2 alpha / (rho c) from them
   void *d_c0 = nullptr, *d_rho0 = nullptr;

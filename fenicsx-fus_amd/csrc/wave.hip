@@ -126,7 +126,7 @@ static int model_setup(fus_model* m, const void* c0_, const void* rho0_, const v
   if (lossy)
     FUSCHK(upload(pool, &d_coef2, coef2, st));
   FUSCHK(upload(pool, &d_mcoef, mcoef, st));
-  m->coef = d_coef, m->coef2 = d_coef2;
+  m->coef = d_coef, m->coef2 = d_coef2, m->mcoef = d_mcoef;
   T *d_c0i, *d_rho0i;
   FUSCHK(upload(pool, &d_c0i, c0i, st));
   FUSCHK(upload(pool, &d_rho0i, rho0i, st));
@@ -1068,6 +1068,128 @@ static int model_after_step(fus_model* m, double t)
   return FUS_OK;
 }
 
+// ---- relaxation absorption (fus_model_set_relaxation, fusmi.h) ----
+// One sub-step of length h on the resident (v0, z): an ordinary launch on the model's stream, nothing when relaxation is
+// off.  The coefficients p, e, g of wave_kernels.hpp are formed here in double and rounded once to T.  v0 changes, so the
+// boundary terms the last stage left for the next step's first stage (boundary_next) are stale afterwards.
+template <typename T, int R>
+static int launch_relax(fus_model* m, double h)
+{
+  const int64_t n = m->op->L.n_internal;
+  const int64_t nvec = n / (16 / (int64_t)sizeof(T));
+  RelaxCoef<T, R> c;
+  for (int k = 0; k < R; ++k)
+  {
+    const double hw = h * m->rx.omega[k], d = 1.0 + 0.5 * hw;
+    c.p[k] = (T)((1.0 - 0.5 * hw) / d), c.e[k] = (T)((0.5 * h) / d), c.g[k] = (T)(hw / d);
+  }
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nvec + 255) / 256, (int64_t)m->ctx->num_cus * 8));
+  hipLaunchKernelGGL((k_relax_substep<T, R>), dim3(grid), dim3(256), 0, m->ctx->stream, nvec, n, static_cast<T*>(m->v0),
+                     m->rx.z.as<T>(), m->rx.A.as<const T>(), c);
+  return FUS_OK;
+}
+
+template <typename T>
+static int launch_relax_r(fus_model* m, double h)
+{
+  return with_kind<1, 2, 3, 4>(m->rx.nrelax, [&](auto R) { return launch_relax<T, decltype(R)::value>(m, h); });
+}
+
+static int relax_apply(fus_model* m, double h)
+{
+  if (m->rx.nrelax == 0)
+    return FUS_OK;
+  {
+    ProfScope ps(m->ctx, "relax");
+    FUSCHK(FUS_BY_DTYPE(m->op->dtype, launch_relax_r, m, h));
+  }
+  HIPCHK(hipGetLastError());
+  m->bnd_valid = false;
+  return FUS_OK;
+}
+
+// a member of an in-process group whose strengths still wait for the sharers' parts must not step
+static int relax_ready(const fus_model* m)
+{
+  return m->rx.pending ? fail(FUS_ERR_STATE, "relaxation strengths are not summed over the sharers: call "
+                                             "fus_group_relaxation_finish on the group first")
+                       : FUS_OK;
+}
+
+// A_nu = num_nu / den on the planes of R (in place), once both are complete
+template <typename T>
+static int relax_divide(fus_model* m, ModelRelax& R)
+{
+  const int64_t n = m->op->L.n_internal;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)m->ctx->num_cus * 8));
+  hipLaunchKernelGGL((k_relax_strength<T>), dim3(grid), dim3(256), 0, m->ctx->stream, n, R.nrelax, R.A.as<T>(),
+                     R.den.as<const T>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  R.den.reset();
+  R.pending = false;
+  return FUS_OK;
+}
+
+// The planes are built beside those in force and replace them at the end: an error leaves the model as it was.
+template <typename T>
+static int model_set_relaxation(fus_model* m, int nrelax, const double* omega, const void* strength_)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t n = op->L.n_internal, nc = op->ncells;
+  const T* a = static_cast<const T*>(strength_);
+  for (int64_t i = 0; i < (int64_t)nrelax * nc; ++i)
+    if (!(a[i] >= T(0)) || !std::isfinite((double)a[i]))
+      return fail(FUS_ERR_ARG, "fus_model_set_relaxation: negative or non-finite strength of process " + std::to_string(i / nc)
+                                   + " in cell " + std::to_string(i % nc));
+  HIPCHK(hipStreamSynchronize(st));
+  const char* what = "relaxation planes (fus_model_set_relaxation)";
+  ModelRelax R;
+  R.nrelax = nrelax;
+  for (int k = 0; k < nrelax; ++k)
+    R.omega[k] = omega[k];
+  FUSCHK(R.z.alloc((size_t)nrelax * n * sizeof(T), what));
+  FUSCHK(R.A.alloc((size_t)nrelax * n * sizeof(T), what));
+  FUSCHK(R.den.alloc((size_t)n * sizeof(T), what));
+  DevBuf ones, coef;
+  FUSCHK(ones.alloc((size_t)n * sizeof(T), what));
+  FUSCHK(coef.alloc((size_t)nc * sizeof(T), what));
+  HIPCHK(hipMemsetAsync(R.z.p, 0, R.z.bytes, st));
+  HIPCHK(hipMemsetAsync(R.A.p, 0, R.A.bytes, st));
+  HIPCHK(hipMemsetAsync(R.den.p, 0, R.den.bytes, st));
+  hipLaunchKernelGGL((k_fill<T>), dim3(1024), dim3(256), 0, st, n, ones.as<T>(), T(1));
+  // the lumped vectors, this rank's cells: den = M(1/(rho c^2)) 1, num_nu = M(a_nu/(rho c^2)) 1 (into A_nu)
+  std::vector<T> mc(nc), cf(nc);
+  HIPCHK(hipMemcpyAsync(mc.data(), m->mcoef, (size_t)nc * sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  FUSCHK(d_apply_internal(op, OP_MASS, m->mcoef, ones.p, R.den.p));
+  for (int k = 0; k < nrelax; ++k)
+  {
+    for (int64_t e = 0; e < nc; ++e)
+      cf[e] = a[(int64_t)k * nc + op->L.cell_perm[e]] * mc[e];
+    HIPCHK(hipMemcpyAsync(coef.p, cf.data(), (size_t)nc * sizeof(T), hipMemcpyHostToDevice, st));
+    FUSCHK(d_apply_internal(op, OP_MASS, coef.p, ones.p, R.A.as<T>() + (int64_t)k * n));
+    HIPCHK(hipStreamSynchronize(st));   // cf is rewritten
+  }
+  // the sharers' parts: over RCCL here (collective), in a group by fus_group_relaxation_finish
+  const bool multi = !op->neigh.empty();
+  if (multi && !m->ctx->local_group)
+  {
+    FUSCHK(d_halo_sum(op, R.den.p));
+    for (int k = 0; k < nrelax; ++k)
+      FUSCHK(d_halo_sum(op, R.A.as<T>() + (int64_t)k * n));
+  }
+  if (multi && m->ctx->local_group)
+    R.pending = true;
+  else
+    FUSCHK(relax_divide<T>(m, R));
+  HIPCHK(hipStreamSynchronize(st));
+  m->rx = std::move(R);
+  model_changed(m, CHANGED_STATE);   // the mass actions went through the partial slab
+  return FUS_OK;
+}
+
 // The stages of one step of the members' RK order from time t (Linear.hpp:273-295; ops[i] = ms[i]->op): per stage the first
 // halves of all members (they end with the pack), the exchange, the second halves.  A single object -- one rank, or several
 // over RCCL -- exchanges on the comm stream (nothing without neighbours), the members of an in-process group through
@@ -1145,26 +1267,33 @@ static int d_model_step(fus_model** ms, fus_op** ops, int n, double t, double dt
   return FUS_OK;
 }
 
-// What ends a step whose last stage has run, t_next the new time: at the orders 1-3 the accumulated solution becomes the
-// next step's start state (RK4's last stage writes u0, v0 itself); then the receiver record and the monitor sample
-static int wave_step_end(fus_model** ms, int n, double t_next)
+// What ends a step of length dt whose last stage has run, t_next the new time: at the orders 1-3 the accumulated solution
+// becomes the next step's start state (RK4's last stage writes u0, v0 itself); the trailing relaxation half-step on that
+// state; then the receiver record and the monitor sample, which see the synchronised state
+static int wave_step_end(fus_model** ms, int n, double dt, double t_next)
 {
   for (int i = 0; i < n; ++i)
   {
     fus_model* m = ms[i];
     if (m->rk_order != 4)
       std::swap(m->u_, m->u0), std::swap(m->v_, m->v0);
+    FUSCHK(relax_apply(m, 0.5 * dt));
     FUSCHK(model_record_step(m, t_next));
     FUSCHK(model_after_step(m, t_next));
   }
   return FUS_OK;
 }
 
-// One step of n models from time t, state in (u0, v0) on entry and exit; the callers keep the clock and pass the new time
+// One step of n models from time t, state in (u0, v0) on entry and exit; the callers keep the clock and pass the new time.
+// With relaxation (Strang splitting): a half-step of it, the RK step as it is, the second half-step in wave_step_end --
+// two launches per step, both outside the graph capture of d_model_step, so a run split into several calls gives the
+// bits of one call.
 static int wave_step(fus_model** ms, fus_op** ops, int n, double t, double dt, double t_next)
 {
+  for (int i = 0; i < n; ++i)
+    FUSCHK(relax_apply(ms[i], 0.5 * dt));
   FUSCHK(d_model_step(ms, ops, n, t, dt));
-  return wave_step_end(ms, n, t_next);
+  return wave_step_end(ms, n, dt, t_next);
 }
 
 static int d_stage_end(fus_model* m, int i, double t, double dt) { return FUS_BY_DTYPE(m->op->dtype, stage_end, m, i, t, dt); }
@@ -1302,6 +1431,8 @@ int fus_group_rk4_steps(fus_model** ms, int n, double t0, double dt, int64_t nst
   for (int i = 1; i < n; ++i)
     if (ms[i]->rk_order != ms[0]->rk_order || ms[i]->kind != ms[0]->kind || ms[i]->op->dtype != ms[0]->op->dtype)
       return fail(FUS_ERR_ARG, "group members differ in rk_order, model kind or scalar type");
+  for (int i = 0; i < n; ++i)
+    FUSCHK(relax_ready(ms[i]));
   std::vector<fus_op*> ops(n);
   for (int i = 0; i < n; ++i)
     ops[i] = ms[i]->op;
@@ -1349,6 +1480,9 @@ int fus_model_stage_begin(fus_model* m, int stage, double t, double dt)
     return fail(FUS_ERR_STATE, "fus_model_setup_finish and fus_model_init come first");
   if (stage < 0 || stage >= m->rk_order)
     return fail(FUS_ERR_ARG, "stage out of range");
+  FUSCHK(relax_ready(m));
+  if (stage == 0)
+    FUSCHK(relax_apply(m, 0.5 * dt));   // the leading half-step (wave_step)
   FUSCHK(FUS_BY_DTYPE(m->op->dtype, stage_begin, m, stage, t, dt));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));   // the send buffer is complete on return
   return FUS_OK;
@@ -1360,7 +1494,7 @@ int fus_model_stage_end(fus_model* m, int stage, double t, double dt)
   if (stage < 0 || stage >= m->rk_order)
     return fail(FUS_ERR_ARG, "stage out of range");
   FUSCHK(d_stage_end(m, stage, t, dt));
-  return stage == m->rk_order - 1 ? wave_step_end(&m, 1, t + dt) : FUS_OK;
+  return stage == m->rk_order - 1 ? wave_step_end(&m, 1, dt, t + dt) : FUS_OK;
 }
 
 int fus_model_set_rk_order(fus_model* m, int order)
@@ -1394,6 +1528,8 @@ int fus_model_init(fus_model* m)
   const size_t bytes = (size_t)m->op->L.n_internal * m->op->ts;
   for (void* v : {m->u0, m->v0, m->u_, m->v_, m->un, m->vn, m->b})
     HIPCHK(hipMemsetAsync(v, 0, bytes, m->ctx->stream));
+  if (m->rx.z)   // the memory variables start from rest with the fields (fus_model_set leaves them alone)
+    HIPCHK(hipMemsetAsync(m->rx.z.p, 0, m->rx.z.bytes, m->ctx->stream));
   m->initialised = true;
   model_changed(m, CHANGED_STATE);
   return FUS_OK;
@@ -1574,6 +1710,7 @@ int fus_model_rk4(fus_model* m, double t0, double tf_, double dt_, int64_t* nste
     return fail(FUS_ERR_ARG, "dt must be positive");
   if (m->ctx->local_group)
     return fail(FUS_ERR_STATE, "in-process transport: use fus_group_rk4_steps");
+  FUSCHK(relax_ready(m));
   HIPCHK(hipSetDevice(m->ctx->device));
   int64_t step = 0;
   FUSCHK(FUS_BY_DTYPE(m->op->dtype, model_rk, m, t0, tf_, dt_, &step));
@@ -1591,6 +1728,7 @@ int fus_model_rk4_steps(fus_model* m, double t0, double dt, int64_t nsteps)
     return fail(FUS_ERR_STATE, "fus_model_init (or fus_model_set) must be called before rk4");
   if (m->ctx->local_group)
     return fail(FUS_ERR_STATE, "in-process transport: use fus_group_rk4_steps");
+  FUSCHK(relax_ready(m));
   HIPCHK(hipSetDevice(m->ctx->device));
   double t = t0;
   for (int64_t s = 0; s < nsteps; ++s)
@@ -1655,6 +1793,118 @@ int fus_model_set_source_signals(fus_model* m, int64_t nchan, int64_t nsamp, dou
   HIPCHK(hipSetDevice(m->ctx->device));
   return FUS_BY_DTYPE(m->op->dtype, model_set_source_signals, m, nchan, nsamp, t_first, ds, signals, channel, amplitude,
                       delay, space);
+}
+
+// ---- relaxation absorption (fusmi.h) ----
+int fus_model_set_relaxation(fus_model* m, int nrelax, const double* omega, const void* strength)
+{
+  if (!m)
+    return fail(FUS_ERR_ARG, "null model");
+  if (nrelax < 0 || nrelax > 4)
+    return fail(FUS_ERR_ARG, "fus_model_set_relaxation: nrelax is 0 (off) to 4");
+  if (nrelax > 0 && strength && !omega)
+    return fail(FUS_ERR_ARG, "fus_model_set_relaxation: null omega");
+  if (!m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_set_relaxation: the model's setup is not finished");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  if (nrelax == 0 || !strength)
+  {
+    HIPCHK(hipStreamSynchronize(m->ctx->stream));
+    const bool was_on = m->rx.nrelax > 0;
+    m->rx = ModelRelax{};
+    if (was_on)
+      model_changed(m, CHANGED_STATE);
+    return FUS_OK;
+  }
+  for (int k = 0; k < nrelax; ++k)
+    if (!(omega[k] > 0.0) || !std::isfinite(omega[k]))
+      return fail(FUS_ERR_ARG, "fus_model_set_relaxation: relaxation frequency " + std::to_string(k) + " is not positive and finite");
+  if (!m->op->neigh.empty() && m->ctx->external_transport)
+    return fail(FUS_ERR_STATE, "fus_model_set_relaxation: a model with neighbours under the external transport is not "
+                               "supported (the strengths' sums over the sharers have no entry points there)");
+  return FUS_BY_DTYPE(m->op->dtype, model_set_relaxation, m, nrelax, omega, strength);
+}
+
+static int relax_plane(fus_model* m, int nu, const void* p, int space, void** plane)
+{
+  if (!m || !p || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_model_relaxation_get / _set: bad model, pointer or space");
+  if (m->rx.nrelax == 0)
+    return fail(FUS_ERR_STATE, "relaxation is off (fus_model_set_relaxation)");
+  if (nu < 0 || nu >= m->rx.nrelax)
+    return fail(FUS_ERR_ARG, "fus_model_relaxation_get / _set: process index outside 0..nrelax-1");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  *plane = m->rx.z.as<char>() + (size_t)nu * m->op->L.n_internal * m->op->ts;
+  return FUS_OK;
+}
+
+int fus_model_relaxation_get(fus_model* m, int nu, void* out, int space)
+{
+  void* plane;
+  FUSCHK(relax_plane(m, nu, out, space, &plane));
+  return FUS_BY_DTYPE(m->op->dtype, model_getset, m, plane, out, space, false);
+}
+
+int fus_model_relaxation_set(fus_model* m, int nu, const void* in, int space)
+{
+  void* plane;
+  FUSCHK(relax_plane(m, nu, in, space, &plane));
+  return FUS_BY_DTYPE(m->op->dtype, model_getset, m, plane, const_cast<void*>(in), space, true);
+}
+
+int fus_model_relaxation_strength(fus_model* m, int nu, void* out, int space)
+{
+  void* plane;
+  FUSCHK(relax_plane(m, nu, out, space, &plane));
+  FUSCHK(relax_ready(m));
+  plane = m->rx.A.as<char>() + (static_cast<char*>(plane) - m->rx.z.as<char>());
+  return FUS_BY_DTYPE(m->op->dtype, model_getset, m, plane, out, space, false);
+}
+
+int fus_model_relaxation_apply(fus_model* m, double h)
+{
+  if (!m || !(h >= 0.0) || !std::isfinite(h))
+    return fail(FUS_ERR_ARG, "fus_model_relaxation_apply: bad model or sub-step length");
+  if (!m->initialised || !m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_init (or fus_model_set) must be called before fus_model_relaxation_apply");
+  FUSCHK(relax_ready(m));
+  HIPCHK(hipSetDevice(m->ctx->device));
+  FUSCHK(relax_apply(m, h));
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_group_relaxation_finish(fus_model** ms, int n)
+{
+  if (!ms || n < 1)
+    return fail(FUS_ERR_ARG, "bad group");
+  for (int i = 0; i < n; ++i)
+    if (!ms[i] || ms[i]->rx.nrelax != ms[0]->rx.nrelax || ms[i]->op->dtype != ms[0]->op->dtype)
+      return fail(FUS_ERR_ARG, "fus_group_relaxation_finish: group members differ in nrelax or scalar type");
+  for (int i = 0; i < n; ++i)
+    if (ms[i]->rx.nrelax > 0 && !ms[i]->rx.pending)
+      return fail(FUS_ERR_STATE, "fus_group_relaxation_finish: a member's strengths are complete already");
+  if (ms[0]->rx.nrelax == 0)
+    return FUS_OK;
+  // den and the nrelax numerators, summed over the sharers after the pattern of thermal_sum
+  std::vector<fus_op*> ops(n);
+  const size_t plane = (size_t)ms[0]->op->ts;
+  for (int k = 0; k <= ms[0]->rx.nrelax; ++k)
+  {
+    auto vec = [&](fus_model* m) -> void*
+    { return k == 0 ? m->rx.den.p : m->rx.A.as<char>() + (size_t)(k - 1) * m->op->L.n_internal * plane; };
+    for (int i = 0; i < n; ++i)
+    {
+      ops[i] = ms[i]->op;
+      FUSCHK(d_halo_pack(ops[i], vec(ms[i])));
+    }
+    FUSCHK(halo_exchange_local(ops.data(), n));
+    for (int i = 0; i < n; ++i)
+      FUSCHK(d_halo_unpack(ops[i], vec(ms[i])));
+  }
+  for (int i = 0; i < n; ++i)
+    FUSCHK(FUS_BY_DTYPE(ms[i]->op->dtype, relax_divide, ms[i], ms[i]->rx));
+  return FUS_OK;
 }
 
 int fus_model_get_mass(fus_model* m, void* out)

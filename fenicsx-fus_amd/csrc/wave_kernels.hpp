@@ -284,6 +284,110 @@ k_monitor_accumulate(int64_t nvec, int64_t n, int first, const T* __restrict__ x
   }
 }
 
+// ---- relaxation absorption (fus_model_set_relaxation, fusmi.h) -------------------------------------------------
+// One sub-step of length h of the local system  v' = -sum_nu A_nu (v - w_nu z_nu),  z_nu' = v - w_nu z_nu  by the
+// trapezoidal rule, in closed form (d = 1 + h w / 2;  p = (1 - h w / 2) / d,  e = (h / 2) / d,  g = h w / d):
+//   s = sum_nu A_nu e_nu,   r = sum_nu (A_nu g_nu) z_nu                      (ascending nu)
+//   v+ = ((1 - s) v + r) / (1 + s),   z_nu+ = p_nu z_nu + e_nu (v + v+)
+// p, e, g are computed on the host in double, rounded once to T and arrive by value.  The arithmetic stands once, on
+// registers, for the 16-byte path and the DOF-by-DOF tail, written out without contraction like stage_update_regs: a
+// DOF's bits do not depend on the path that took it.  s == 0 (no strength at this DOF, padding): v keeps its bits.
+template <typename T, int R>
+struct RelaxCoef
+{
+  T p[R], e[R], g[R];
+};
+
+template <typename T, int R>
+__device__ __forceinline__ void relax_substep_regs(T& v, T (&z)[R], const T (&A)[R], const RelaxCoef<T, R>& c)
+{
+#pragma clang fp contract(off)
+  T s = A[0] * c.e[0], r = (A[0] * c.g[0]) * z[0];
+#pragma unroll
+  for (int k = 1; k < R; ++k)
+  {
+    s = s + A[k] * c.e[k];
+    r = r + (A[k] * c.g[k]) * z[k];
+  }
+  const T vp = s == T(0) ? v : ((T(1) - s) * v + r) / (T(1) + s);
+  const T vs = v + vp;
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+    z[k] = c.p[k] * z[k] + c.e[k] * vs;
+  v = vp;
+}
+
+// The streaming form of k_monitor_accumulate: a thread takes 16 bytes of consecutive DOFs (2 doubles / 4 floats) of v
+// and of every plane z_nu, A_nu (n = n_internal each, a multiple of 16); all accesses 16-byte and non-temporal, one
+// read of A_nu, one read and one write of v and z_nu: (3 R + 2) sizeof(T) bytes per DOF.  R is a template parameter:
+// the plane loops unroll and nothing is indexed at run time (no scratch).  No LDS, no atomics.  DOFs past the last
+// whole vector (none while n is a multiple of 16) go one by one through the same arithmetic.
+template <typename T, int R>
+__global__ void __launch_bounds__(256)
+k_relax_substep(int64_t nvec, int64_t n, T* __restrict__ v, T* __restrict__ z, const T* __restrict__ A,
+                const RelaxCoef<T, R> c)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+  {
+    TV* pv = reinterpret_cast<TV*>(v + i * VEC);
+    TV vv = __builtin_nontemporal_load(pv);
+    TV zv[R], Av[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+    {
+      zv[k] = __builtin_nontemporal_load(reinterpret_cast<const TV*>(z + k * n + i * VEC));
+      Av[k] = __builtin_nontemporal_load(reinterpret_cast<const TV*>(A + k * n + i * VEC));
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+    {
+      T x = vv[j], zz[R], aa[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        zz[k] = zv[k][j], aa[k] = Av[k][j];
+      relax_substep_regs<T, R>(x, zz, aa, c);
+      vv[j] = x;
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        zv[k][j] = zz[k];
+    }
+    __builtin_nontemporal_store(vv, pv);
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+      __builtin_nontemporal_store(zv[k], reinterpret_cast<TV*>(z + k * n + i * VEC));
+  }
+  // the tail [nvec VEC, n): fewer than VEC DOFs, the first threads of block 0
+  const int64_t d = nvec * VEC + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < VEC && d < n)
+  {
+    T x = v[d], zz[R], aa[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+      zz[k] = z[k * n + d], aa[k] = A[k * n + d];
+    relax_substep_regs<T, R>(x, zz, aa, c);
+    v[d] = x;
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+      z[k * n + d] = zz[k];
+  }
+}
+
+// Per-DOF strengths from the lumped mass actions: A_nu = num_nu / den where den != 0, 0 in the padding slots
+// (num = M(a_nu / (rho c^2)) 1 in place, den = M(1 / (rho c^2)) 1, both summed over the sharers beforehand)
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_relax_strength(int64_t n, int nplanes, T* __restrict__ A, const T* __restrict__ den)
+{
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+  {
+    const T d = den[i];
+    for (int k = 0; k < nplanes; ++k)
+      A[k * n + i] = d != T(0) ? A[k * n + i] / d : T(0);
+  }
+}
+
 // Monitor read-out in internal numbering: out = (num * plane) / den, or its square root (RMS), rounded to T.
 template <typename T>
 __global__ void __launch_bounds__(256)

@@ -256,6 +256,51 @@ class _SpectralExplicit:
         check(lib().fus_model_set_source_signals(self.h, C.c_int64(nchan), C.c_int64(nsamp), C.c_double(t_first),
                                                  C.c_double(ds), ptr(s), ptr(ch), ptr(a), ptr(d), C.c_int(_abi.FUS_HOST)))
 
+    # ---- relaxation absorption: power-law tissue absorption (fusmi.h; fits: fenicsxfus_amd.absorption) ----
+    def set_relaxation(self, freqs_hz, strength):
+        """Add ``R = len(freqs_hz)`` (at most 4) relaxation processes with the relaxation frequencies ``freqs_hz`` (Hz)
+        and the strengths ``strength`` (1/s): [R] for a homogeneous medium, or [R, ncells] per cell (a CellFunction row
+        each).  :func:`fenicsxfus_amd.absorption.fit_power_law` yields both for alpha = alpha0 f^y.  ``c0`` is then
+        the high-frequency sound speed.  The memory variables start from 0; u and v are kept.  Several ranks: collective
+        under RCCL; the members of an in-process group call :func:`group_relaxation_finish` afterwards."""
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64)))
+        nc = self.mesh.num_cells
+        try:
+            a = np.array([np.broadcast_to(np.asarray(_array(row), dtype=np.float64), (nc,)) for row in strength])
+        except (TypeError, ValueError) as e:
+            raise _abi.FusError(f"set_relaxation: every process takes one strength or {nc} (one per cell): {e}") from None
+        if f.ndim != 1 or a.shape != (len(f), nc):
+            raise _abi.FusError(f"set_relaxation: {len(f)} frequencies but strengths of shape {a.shape}")
+        a = np.ascontiguousarray(a, dtype=self.data.dtype)
+        w = np.ascontiguousarray(2.0 * np.pi * f)
+        check(lib().fus_model_set_relaxation(self.h, C.c_int(len(f)), ptr(w), ptr(a)))
+
+    def clear_relaxation(self):
+        """Relaxation off: the planes are freed, a step enqueues what it did before."""
+        check(lib().fus_model_set_relaxation(self.h, C.c_int(0), None, None))
+
+    def relaxation_state(self, nu: int):
+        """The memory variable z_nu as an array over the model's DOFs (checkpoints, tests)."""
+        z = np.zeros(self.data.ndofs, dtype=self.data.dtype)
+        check(lib().fus_model_relaxation_get(self.h, C.c_int(nu), ptr(z), C.c_int(_abi.FUS_HOST)))
+        return z
+
+    def set_relaxation_state(self, nu: int, z):
+        z = np.ascontiguousarray(_array(z), dtype=self.data.dtype)
+        if z.shape != (self.data.ndofs,):
+            raise _abi.FusError(f"set_relaxation_state: expected {self.data.ndofs} values, one per DOF, got shape {z.shape}")
+        check(lib().fus_model_relaxation_set(self.h, C.c_int(nu), ptr(z), C.c_int(_abi.FUS_HOST)))
+
+    def relaxation_strength(self, nu: int):
+        """The per-DOF strength A_nu as the sub-step reads it (diagnostics, tests)."""
+        a = np.zeros(self.data.ndofs, dtype=self.data.dtype)
+        check(lib().fus_model_relaxation_strength(self.h, C.c_int(nu), ptr(a), C.c_int(_abi.FUS_HOST)))
+        return a
+
+    def relaxation_apply(self, h: float):
+        """One relaxation sub-step of length ``h`` on the resident state (the stepping entries run two of dt / 2 per step)."""
+        check(lib().fus_model_relaxation_apply(self.h, C.c_double(h)))
+
     def u_sol(self):
         self._pull()
         return self.u_n
@@ -335,3 +380,9 @@ def group_rk4_steps(models, t0: float, dt: float, nsteps: int):
     """In-process transport: advance all slab models in lock-step (tests)."""
     arr = (C.c_void_p * len(models))(*[m.h for m in models])
     check(lib().fus_group_rk4_steps(arr, C.c_int(len(models)), C.c_double(t0), C.c_double(dt), C.c_int64(nsteps)))
+
+
+def group_relaxation_finish(models):
+    """In-process transport: after every member's set_relaxation, add the sharers' parts of the relaxation strengths."""
+    arr = (C.c_void_p * len(models))(*[m.h for m in models])
+    check(lib().fus_group_relaxation_finish(arr, C.c_int(len(models))))

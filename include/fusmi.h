@@ -411,6 +411,45 @@ int fus_model_set_source_signals(fus_model* model, int64_t nchan, int64_t nsamp,
                                  const double* signals, const int32_t* channel, const void* amplitude, const void* delay,
                                  int space);
 
+/* ---- relaxation absorption: power-law tissue absorption in the wave models -----------------------------------------
+ * The wave models absorb thermoviscously only (delta0: alpha ~ f^2); soft tissue follows alpha ~ f^y with y = 1..1.3.
+ * nrelax <= 4 relaxation processes with global angular relaxation frequencies w_nu > 0 (1/s) and per-cell strengths
+ * a_nu >= 0 (1/s), added to any of the three models, fit such a law over a band (fenicsxfus_amd.absorption.fit_power_law):
+ *   (1/(rho c^2)) [ u_tt + sum_nu a_nu (u_t - w_nu z_nu) ] = (the model's right-hand side),
+ *   z_nu' = u_t - w_nu z_nu,   z_nu(0) = 0     (one memory variable per process and DOF)
+ * A plane wave e^{i(w t - k x)} then has  k = (w/c) sqrt(1 + sum_nu a_nu / (w_nu + i w)),
+ *   alpha = -Im k ~ (1/2c) sum_nu a_nu w^2 / (w_nu^2 + w^2).
+ * c0 is the HIGH-frequency sound speed of such a medium; the low-frequency one is c0 / sqrt(1 + sum_nu a_nu / w_nu).
+ * Per DOF the strength is A_nu = (M(a_nu/(rho c^2)) 1) / (M(1/(rho c^2)) 1), numerator and denominator summed over
+ * the sharers before the division; 0 in the padding slots.
+ * Time stepping: Strang splitting around every step of every RK order -- a relaxation sub-step of length dt/2, the RK
+ * step as it is, a second sub-step of dt/2, then the receiver record and the monitor sample (they see the synchronised
+ * state).  The sub-step is the trapezoidal rule on  v' = -sum A_nu (v - w_nu z_nu), z_nu' = v - w_nu z_nu  in closed
+ * form: unconditionally stable, it never increases v^2/2 + sum_nu A_nu w_nu z_nu^2 / 2.  The absorption is second order
+ * in dt.  Two launches of one streaming kernel per step (profile name "relax"), (3 nrelax + 2) sizeof(T) bytes per DOF
+ * each, outside the graph of option "graph"; with relaxation off a step enqueues nothing new.
+ *   fus_model_set_relaxation    omega: double[nrelax]; strength: host, T[nrelax][ncells] in the caller's cell order.
+ *                               nrelax = 0 or strength = NULL switches relaxation off and frees the planes.  Otherwise
+ *                               the memory variables start from 0.  Legal once the setup is finished (FUS_ERR_STATE
+ *                               before) and between steps; u and v are kept.  nrelax outside 0..4, w_nu <= 0 or not
+ *                               finite, a negative or non-finite strength -> FUS_ERR_ARG, the model stays as it was.
+ *   fus_model_relaxation_get / _set   z_nu (nu = 0..nrelax-1), T[ndofs] in caller numbering, host or device: for
+ *                               checkpoints and tests.  FUS_ERR_STATE while relaxation is off.  fus_model_init zeroes
+ *                               the z_nu, fus_model_set leaves them alone.
+ *   fus_model_relaxation_strength     A_nu as the sub-step reads it, T[ndofs] in caller numbering (diagnostics, tests)
+ *   fus_model_relaxation_apply  one sub-step of length h >= 0 on the current state (what the stepping entries call)
+ * Several ranks: on a single object with neighbours under RCCL fus_model_set_relaxation is collective (it sums the
+ * nrelax + 1 lumped vectors over the sharers).  The members of an in-process group call fus_model_set_relaxation each
+ * and then fus_group_relaxation_finish once; stepping a member before that -> FUS_ERR_STATE.  A model with neighbours
+ * under the external transport -> FUS_ERR_STATE (no entry points for the sums there).  The sub-step itself needs no
+ * exchange: the sharers of a DOF hold identical v and identical A_nu. */
+int fus_model_set_relaxation(fus_model* model, int nrelax, const double* omega, const void* strength /* T[nrelax][ncells] */);
+int fus_model_relaxation_get(fus_model* model, int nu, void* out, int space);
+int fus_model_relaxation_set(fus_model* model, int nu, const void* in, int space);
+int fus_model_relaxation_strength(fus_model* model, int nu, void* out, int space);
+int fus_model_relaxation_apply(fus_model* model, double h);
+int fus_group_relaxation_finish(fus_model** models, int n);
+
 /* ---- bioheat: Pennes equation and CEM43 thermal dose on the operator's mesh ---------------------------------------
  * What a focused-ultrasound user computes from the pressure maps: the temperature rise the beam causes and the thermal
  * dose it leaves.  (The reference has no thermal model; this section replaces nothing there.)

@@ -22,6 +22,7 @@
 // fusmi::Error (the C ABI's code and message); nothing else is added on top of the C ABI.
 // Header-only, C++17, no dependency beyond fusmi.h.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -302,6 +303,32 @@ public:
                           const std::int32_t* channel = nullptr, const T* amp = nullptr, const T* delay = nullptr)
   {
     check(fus_model_set_source_signals(h_, nchan, nsamp, t_first, ds, signals, channel, amp, delay, FUS_HOST));
+  }
+  // relaxation absorption (fusmi.h): freqs.size() <= 4 processes with the relaxation frequencies freqs (Hz) and the
+  // strengths strength[nu * ncells + cell] (1/s), or one strength per process for a homogeneous medium; the speed of
+  // sound given to the constructor is then the high-frequency one.  The memory variables start from 0.
+  void set_relaxation(const std::vector<double>& freqs, const std::vector<T>& strength)
+  {
+    const std::size_t R = freqs.size(), nc = (std::size_t)d_->ncells();
+    std::vector<double> omega(R);
+    for (std::size_t k = 0; k < R; ++k)
+      omega[k] = 2.0 * 3.14159265358979323846 * freqs[k];
+    std::vector<T> a(R * nc);
+    if (strength.size() == R)
+      for (std::size_t k = 0; k < R; ++k)
+        std::fill(a.begin() + k * nc, a.begin() + (k + 1) * nc, strength[k]);
+    else if (strength.size() == R * nc)
+      a = strength;
+    else
+      throw Error(FUS_ERR_ARG, "set_relaxation: one strength per process, or one per process and cell");
+    check(fus_model_set_relaxation(h_, (int)R, omega.data(), a.data()));
+  }
+  void clear_relaxation() { check(fus_model_set_relaxation(h_, 0, nullptr, nullptr)); }
+  std::vector<T> relaxation_state(int nu) const   // z_nu, caller numbering
+  {
+    std::vector<T> z((size_t)d_->ndofs());
+    check(fus_model_relaxation_get(h_, nu, z.data(), FUS_HOST));
+    return z;
   }
   fus_model* handle() const { return h_; }
   ~SpectralModel() { fus_model_destroy(h_); }
