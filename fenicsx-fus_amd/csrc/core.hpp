@@ -170,6 +170,16 @@ struct FUS_HIDDEN ModelRelax
   bool pending = false;
 };
 
+// absorbing layers (fus_model_set_sponge): the damping rate sigma per DOF in internal numbering (padding slots 0) and the
+// ascending list of the tiles -- 256 16-byte vectors of the internal vector each -- that hold a nonzero sigma; the
+// sub-step kernel runs over that list.  Off: both buffers empty, ntiles == 0.
+struct FUS_HIDDEN ModelSponge
+{
+  DevBuf sigma;   // T[n_internal]
+  DevBuf tiles;   // int32[ntiles]
+  int64_t ntiles = 0, ntiles_total = 0, ndofs_active = 0;
+};
+
 // Of the wave model the bioheat unit reads what its two heat-load calls need: op, d_rho0, d_c0 and the monitor's
 // mon.d_mon, mon.n, mon.nharm, mon.every, mon.which.
 struct fus_model
@@ -200,6 +210,7 @@ struct fus_model
   ModelReceivers rc;
   ModelMonitor mon;
   ModelRelax rx;
+  ModelSponge sp;
   void* mcoef = nullptr;   // the mass coefficient 1/(rho c^2), internal cell order (the setup's; in allocs)
   // c0 and rho0 as fus_model_create was given them, internal cell order: fus_thermal_set_heat_from_monitor forms
   // q_coef = 2 alpha / (rho c) from them

@@ -1108,6 +1108,86 @@ static int relax_apply(fus_model* m, double h)
   return FUS_OK;
 }
 
+// ---- absorbing layers (fus_model_set_sponge, fusmi.h) ----
+// One sub-step of length h on the resident (u0, v0) and, with relaxation on, its memory variables: an ordinary launch on
+// the model's stream over the listed tiles, nothing when the sponge is off.  v0 changes, so the boundary terms the last
+// stage left for the next step's first stage are stale afterwards.  No exchange: the sharers of a DOF hold the same sigma.
+template <typename T, int R>
+static int launch_sponge(fus_model* m, double h)
+{
+  const unsigned grid = (unsigned)std::min<int64_t>(m->sp.ntiles, (int64_t)m->ctx->num_cus * 8);
+  hipLaunchKernelGGL((k_sponge_substep<T, R>), dim3(grid), dim3(256), 0, m->ctx->stream, m->sp.ntiles,
+                     m->sp.tiles.as<const int32_t>(), m->op->L.n_internal, h, m->sp.sigma.as<const T>(),
+                     static_cast<T*>(m->u0), static_cast<T*>(m->v0), m->rx.z.as<T>());
+  return FUS_OK;
+}
+
+template <typename T>
+static int launch_sponge_r(fus_model* m, double h)
+{
+  return with_kind<0, 1, 2, 3, 4>(m->rx.nrelax, [&](auto R) { return launch_sponge<T, decltype(R)::value>(m, h); });
+}
+
+static int sponge_apply(fus_model* m, double h)
+{
+  if (m->sp.ntiles == 0)
+    return FUS_OK;
+  {
+    ProfScope ps(m->ctx, "sponge");
+    FUSCHK(FUS_BY_DTYPE(m->op->dtype, launch_sponge_r, m, h));
+  }
+  HIPCHK(hipGetLastError());
+  m->bnd_valid = false;
+  return FUS_OK;
+}
+
+// sigma (host, caller numbering, checked) into a new plane in internal numbering and its tile list, built beside those in
+// force and replacing them at the end: an error leaves the model as it was.  An all-zero sigma switches the sponge off.
+template <typename T>
+static int model_set_sponge(fus_model* m, const void* sigma_)
+{
+  fus_op* op = m->op;
+  hipStream_t st = m->ctx->stream;
+  const int64_t n = op->L.n_internal;
+  const T* s = static_cast<const T*>(sigma_);
+  for (int64_t i = 0; i < op->ndofs; ++i)
+    if (!(s[i] >= T(0)) || !std::isfinite((double)s[i]))
+      return fail(FUS_ERR_ARG, "fus_model_set_sponge: negative or non-finite sigma at DOF " + std::to_string(i));
+  HIPCHK(hipStreamSynchronize(st));
+  const char* what = "sponge plane and tile list (fus_model_set_sponge)";
+  ModelSponge S;
+  FUSCHK(S.sigma.alloc((size_t)n * sizeof(T), what));
+  HIPCHK(hipMemsetAsync(S.sigma.p, 0, S.sigma.bytes, st));
+  FUSCHK(model_getset<T>(m, S.sigma.p, const_cast<void*>(sigma_), FUS_HOST, true));
+  std::vector<T> si((size_t)n);
+  FUSCHK(copy_sync(st, si.data(), S.sigma.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost));
+  const int64_t tile = 256 * (16 / (int64_t)sizeof(T));
+  S.ntiles_total = (n + tile - 1) / tile;
+  std::vector<int32_t> tiles;
+  for (int64_t t = 0; t < S.ntiles_total; ++t)
+  {
+    int64_t cnt = 0;
+    for (int64_t i = t * tile; i < std::min(n, (t + 1) * tile); ++i)
+      cnt += si[i] != T(0);
+    if (cnt > 0)
+      tiles.push_back((int32_t)t);
+    S.ndofs_active += cnt;
+  }
+  S.ntiles = (int64_t)tiles.size();
+  const bool was_on = m->sp.ntiles > 0;
+  if (S.ntiles == 0)
+    S = ModelSponge{};
+  else
+  {
+    FUSCHK(upload(S.tiles, tiles, st, what));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  m->sp = std::move(S);
+  if (was_on || m->sp.ntiles > 0)
+    model_changed(m, CHANGED_STATE);
+  return FUS_OK;
+}
+
 // a member of an in-process group whose strengths still wait for the sharers' parts must not step
 static int relax_ready(const fus_model* m)
 {
@@ -1269,7 +1349,8 @@ static int d_model_step(fus_model** ms, fus_op** ops, int n, double t, double dt
 
 // What ends a step of length dt whose last stage has run, t_next the new time: at the orders 1-3 the accumulated solution
 // becomes the next step's start state (RK4's last stage writes u0, v0 itself); the trailing relaxation half-step on that
-// state; then the receiver record and the monitor sample, which see the synchronised state
+// state and then the trailing sponge half-step (the mirror image of wave_step's order: the composition stays symmetric);
+// then the receiver record and the monitor sample, which see the synchronised state
 static int wave_step_end(fus_model** ms, int n, double dt, double t_next)
 {
   for (int i = 0; i < n; ++i)
@@ -1278,6 +1359,7 @@ static int wave_step_end(fus_model** ms, int n, double dt, double t_next)
     if (m->rk_order != 4)
       std::swap(m->u_, m->u0), std::swap(m->v_, m->v0);
     FUSCHK(relax_apply(m, 0.5 * dt));
+    FUSCHK(sponge_apply(m, 0.5 * dt));
     FUSCHK(model_record_step(m, t_next));
     FUSCHK(model_after_step(m, t_next));
   }
@@ -1287,11 +1369,14 @@ static int wave_step_end(fus_model** ms, int n, double dt, double t_next)
 // One step of n models from time t, state in (u0, v0) on entry and exit; the callers keep the clock and pass the new time.
 // With relaxation (Strang splitting): a half-step of it, the RK step as it is, the second half-step in wave_step_end --
 // two launches per step, both outside the graph capture of d_model_step, so a run split into several calls gives the
-// bits of one call.
+// bits of one call.  With absorbing layers the sponge half-steps go outside the relaxation ones in the same manner.
 static int wave_step(fus_model** ms, fus_op** ops, int n, double t, double dt, double t_next)
 {
   for (int i = 0; i < n; ++i)
+  {
+    FUSCHK(sponge_apply(ms[i], 0.5 * dt));
     FUSCHK(relax_apply(ms[i], 0.5 * dt));
+  }
   FUSCHK(d_model_step(ms, ops, n, t, dt));
   return wave_step_end(ms, n, dt, t_next);
 }
@@ -1481,8 +1566,11 @@ int fus_model_stage_begin(fus_model* m, int stage, double t, double dt)
   if (stage < 0 || stage >= m->rk_order)
     return fail(FUS_ERR_ARG, "stage out of range");
   FUSCHK(relax_ready(m));
-  if (stage == 0)
-    FUSCHK(relax_apply(m, 0.5 * dt));   // the leading half-step (wave_step)
+  if (stage == 0)   // the leading half-steps (wave_step)
+  {
+    FUSCHK(sponge_apply(m, 0.5 * dt));
+    FUSCHK(relax_apply(m, 0.5 * dt));
+  }
   FUSCHK(FUS_BY_DTYPE(m->op->dtype, stage_begin, m, stage, t, dt));
   HIPCHK(hipStreamSynchronize(m->ctx->stream));   // the send buffer is complete on return
   return FUS_OK;
@@ -1904,6 +1992,73 @@ int fus_group_relaxation_finish(fus_model** ms, int n)
   }
   for (int i = 0; i < n; ++i)
     FUSCHK(FUS_BY_DTYPE(ms[i]->op->dtype, relax_divide, ms[i], ms[i]->rx));
+  return FUS_OK;
+}
+
+// ---- absorbing layers (fusmi.h) ----
+int fus_model_set_sponge(fus_model* m, const void* sigma, int space)
+{
+  if (!m || (sigma && space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_model_set_sponge: bad model or space");
+  if (!m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_set_sponge: the model's setup is not finished");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  if (!sigma)
+  {
+    HIPCHK(hipStreamSynchronize(m->ctx->stream));
+    const bool was_on = m->sp.ntiles > 0;
+    m->sp = ModelSponge{};
+    if (was_on)
+      model_changed(m, CHANGED_STATE);
+    return FUS_OK;
+  }
+  std::vector<char> host;   // a device vector is checked, and its tiles listed, on the host
+  if (space == FUS_DEVICE)
+  {
+    host.resize((size_t)m->op->ndofs * m->op->ts);
+    FUSCHK(copy_sync(m->ctx->stream, host.data(), sigma, host.size(), hipMemcpyDeviceToHost));
+    sigma = host.data();
+  }
+  return FUS_BY_DTYPE(m->op->dtype, model_set_sponge, m, sigma);
+}
+
+int fus_model_sponge_get(fus_model* m, void* out, int space)
+{
+  if (!m || !out || (space != FUS_HOST && space != FUS_DEVICE))
+    return fail(FUS_ERR_ARG, "fus_model_sponge_get: bad model, pointer or space");
+  if (m->sp.ntiles == 0)
+    return fail(FUS_ERR_STATE, "the sponge is off (fus_model_set_sponge)");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  return FUS_BY_DTYPE(m->op->dtype, model_getset, m, m->sp.sigma.p, out, space, false);
+}
+
+int fus_model_sponge_apply(fus_model* m, double h)
+{
+  if (!m || !(h >= 0.0) || !std::isfinite(h))
+    return fail(FUS_ERR_ARG, "fus_model_sponge_apply: bad model or sub-step length");
+  if (m->sp.ntiles == 0)
+    return fail(FUS_ERR_STATE, "the sponge is off (fus_model_set_sponge)");
+  if (!m->initialised || !m->setup_done)
+    return fail(FUS_ERR_STATE, "fus_model_init (or fus_model_set) must be called before fus_model_sponge_apply");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  FUSCHK(sponge_apply(m, h));
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  return FUS_OK;
+}
+
+int fus_model_sponge_info(fus_model* m, int64_t* ndofs_active, int64_t* ntiles_active, int64_t* ntiles_total)
+{
+  if (!m)
+    return fail(FUS_ERR_ARG, "null model");
+  if (ndofs_active)
+    *ndofs_active = m->sp.ndofs_active;
+  if (ntiles_active)
+    *ntiles_active = m->sp.ntiles;
+  if (ntiles_total)   // also while the sponge is off: what listing every tile would take
+  {
+    const int64_t tile = 256 * (16 / (int64_t)m->op->ts);
+    *ntiles_total = (m->op->L.n_internal + tile - 1) / tile;
+  }
   return FUS_OK;
 }
 

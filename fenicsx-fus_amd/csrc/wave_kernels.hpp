@@ -388,6 +388,86 @@ k_relax_strength(int64_t n, int nplanes, T* __restrict__ A, const T* __restrict_
   }
 }
 
+// ---- absorbing layers (fus_model_set_sponge, fusmi.h) ----------------------------------------------------------
+// One sub-step of length h of  u' = -sigma u,  v' = -sigma v  (and z_nu' = -sigma z_nu with relaxation on), solved
+// exactly: every field of the DOF is multiplied by g = exp(-sigma h), formed in double and rounded once to T.  The
+// arithmetic stands once, on registers, for the 16-byte path and the DOF-by-DOF tail, without contraction: a DOF's
+// bits do not depend on the path that took it.  sigma == 0 gives g == 1 exactly and the DOF keeps its bits.
+template <typename T, int R>
+__device__ __forceinline__ void sponge_substep_regs(T& u, T& v, T (&z)[R > 0 ? R : 1], T sigma, double h)
+{
+#pragma clang fp contract(off)
+  const T g = (T)exp(-(double)sigma * h);
+  u = g * u;
+  v = g * v;
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+    z[k] = g * z[k];
+}
+
+// A sibling of k_relax_substep that runs over the layers only.  A tile is the 256 consecutive 16-byte vectors one
+// workgroup takes in one trip (512 doubles / 1024 floats); tiles[0..ntiles) is the ascending list of the tiles that
+// hold a nonzero sigma (built by the host at fus_model_set_sponge), the grid strides over that list, and DOFs of
+// unlisted tiles are neither read nor written.  Per DOF of a listed tile: sigma, u, v in, u, v out and every z_nu
+// in and out, (3 + 2 R + 2) sizeof(T) bytes, all 16-byte and non-temporal.  R is a template parameter: the plane
+// loops unroll and nothing is indexed at run time (no scratch).  No LDS, no atomics.  The last tile of the vector
+// may be short (n = n_internal is a multiple of 16, not of the tile): every access is bounded by n, and DOFs past
+// the last whole vector (none while n is a multiple of 16) go one by one through the same arithmetic.
+template <typename T, int R>
+__global__ void __launch_bounds__(256)
+k_sponge_substep(int64_t ntiles, const int32_t* __restrict__ tiles, int64_t n, double h, const T* __restrict__ sigma,
+                 T* __restrict__ u, T* __restrict__ v, T* __restrict__ z)
+{
+  constexpr int VEC = 16 / (int)sizeof(T);
+  constexpr int RN = R > 0 ? R : 1;
+  typedef T TV __attribute__((ext_vector_type(VEC)));
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x)
+  {
+    const int64_t d = ((int64_t)tiles[t] * 256 + threadIdx.x) * VEC;   // this thread's first DOF
+    if (d + VEC <= n)
+    {
+      const TV sv = __builtin_nontemporal_load(reinterpret_cast<const TV*>(sigma + d));
+      TV uv = __builtin_nontemporal_load(reinterpret_cast<const TV*>(u + d));
+      TV vv = __builtin_nontemporal_load(reinterpret_cast<const TV*>(v + d));
+      TV zv[RN];
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        zv[k] = __builtin_nontemporal_load(reinterpret_cast<const TV*>(z + k * n + d));
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+      {
+        T a = uv[j], b = vv[j], zz[RN];
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+          zz[k] = zv[k][j];
+        sponge_substep_regs<T, R>(a, b, zz, sv[j], h);
+        uv[j] = a, vv[j] = b;
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+          zv[k][j] = zz[k];
+      }
+      __builtin_nontemporal_store(uv, reinterpret_cast<TV*>(u + d));
+      __builtin_nontemporal_store(vv, reinterpret_cast<TV*>(v + d));
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        __builtin_nontemporal_store(zv[k], reinterpret_cast<TV*>(z + k * n + d));
+    }
+    else
+      for (int64_t e = d; e < n; ++e)   // fewer than VEC DOFs, one thread of the last tile
+      {
+        T a = u[e], b = v[e], zz[RN];
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+          zz[k] = z[k * n + e];
+        sponge_substep_regs<T, R>(a, b, zz, sigma[e], h);
+        u[e] = a, v[e] = b;
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+          z[k * n + e] = zz[k];
+      }
+  }
+}
+
 // Monitor read-out in internal numbering: out = (num * plane) / den, or its square root (RMS), rounded to T.
 template <typename T>
 __global__ void __launch_bounds__(256)

@@ -33,6 +33,7 @@ SYMBOLS = [
     "fus_model_set_source", "fus_model_set_source_weights", "fus_model_set_source_signals",
     "fus_model_set_relaxation", "fus_model_relaxation_get", "fus_model_relaxation_set", "fus_model_relaxation_apply", "fus_model_relaxation_strength",
     "fus_group_relaxation_finish",
+    "fus_model_set_sponge", "fus_model_sponge_get", "fus_model_sponge_apply", "fus_model_sponge_info",
     "fus_thermal_create", "fus_thermal_destroy", "fus_thermal_init", "fus_thermal_set", "fus_thermal_get",
     "fus_thermal_set_heat", "fus_thermal_set_heat_from_monitor", "fus_thermal_set_heat_from_harmonics",
     "fus_thermal_lambda_max", "fus_thermal_steps",

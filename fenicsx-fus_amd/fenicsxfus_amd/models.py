@@ -301,6 +301,37 @@ class _SpectralExplicit:
         """One relaxation sub-step of length ``h`` on the resident state (the stepping entries run two of dt / 2 per step)."""
         check(lib().fus_model_relaxation_apply(self.h, C.c_double(h)))
 
+    # ---- absorbing layers: a split-step sponge (fusmi.h; profiles: fenicsxfus_amd.sponge) ----
+    def set_sponge(self, sigma):
+        """Damp u, v (and the relaxation memory variables) at the rate ``sigma`` (1/s) per DOF, zero outside the layers:
+        an array or Function over the model's space, e.g. from :func:`fenicsxfus_amd.sponge.layer_sigma`.  Keep tag 2
+        on the faces behind the layers.  u, v and z are kept; an all-zero ``sigma`` is :meth:`clear_sponge`.  Several
+        ranks: the sharers of a DOF must pass the same value (a profile computed from coordinates does); no finish call."""
+        s = np.ascontiguousarray(_array(sigma), dtype=self.data.dtype)
+        if s.shape != (self.data.ndofs,):
+            raise _abi.FusError(f"set_sponge: expected {self.data.ndofs} values, one per DOF, got shape {s.shape}")
+        check(lib().fus_model_set_sponge(self.h, ptr(s), C.c_int(_abi.FUS_HOST)))
+
+    def clear_sponge(self):
+        """Sponge off: the plane and the tile list are freed, a step enqueues what it did before."""
+        check(lib().fus_model_set_sponge(self.h, None, C.c_int(_abi.FUS_HOST)))
+
+    def sponge(self):
+        """The damping rate in force as an array over the model's DOFs."""
+        s = np.zeros(self.data.ndofs, dtype=self.data.dtype)
+        check(lib().fus_model_sponge_get(self.h, ptr(s), C.c_int(_abi.FUS_HOST)))
+        return s
+
+    def sponge_apply(self, h: float):
+        """One sponge sub-step of length ``h`` on the resident state (the stepping entries run two of dt / 2 per step)."""
+        check(lib().fus_model_sponge_apply(self.h, C.c_double(h)))
+
+    def sponge_info(self):
+        """(DOFs with sigma > 0, tiles the sub-step kernel visits, tiles of the whole internal vector)."""
+        nd, na, nt = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().fus_model_sponge_info(self.h, C.byref(nd), C.byref(na), C.byref(nt)))
+        return nd.value, na.value, nt.value
+
     def u_sol(self):
         self._pull()
         return self.u_n

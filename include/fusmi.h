@@ -450,6 +450,50 @@ int fus_model_relaxation_strength(fus_model* model, int nu, void* out, int space
 int fus_model_relaxation_apply(fus_model* model, double h);
 int fus_group_relaxation_finish(fus_model** models, int n);
 
+/* ---- absorbing layers: a split-step sponge in the wave models ------------------------------------------------------
+ * The first-order condition on tag-2 facets (u_t / c) is exact at normal incidence and reflects
+ * (1 - cos th) / (1 + cos th) of the amplitude at the angle th: 17 % at 45 degrees, 33 % at 60.  A steered or focused
+ * beam and above all a point source meet the faces at every angle.  With a damping rate sigma(x) >= 0 (1/s) per DOF,
+ * zero outside the layers, any of the three models solves
+ *   (d/dt + sigma)^2 u = (the model's right-hand side),   i.e.   u_t = v - sigma u,   v_t = RHS(u, v) - sigma v
+ * A plane wave e^{i(w t - k.x)} then has k = (w - i sigma) / c in its own direction, whatever the direction: it decays
+ * as e^{-sigma s / c} along its path, without dispersion and independent of angle and frequency (Cerjan's sponge in
+ * continuous form).  The local impedance mismatch comes from the gradient of sigma alone, which the profile keeps small.
+ * For sigma(d) = sigma_max (d / L)^n over the thickness L the round-trip amplitude reflection off whatever lies behind
+ * the layer is R = exp(-2 sigma_max L / ((n + 1) c)); a design R gives sigma_max = (n + 1) c ln(1 / R) / (2 L)
+ * (fenicsxfus_amd.sponge.layer_sigma builds such profiles from DOF coordinates).
+ * Time stepping: Strang splitting around every step of every RK order, outside the relaxation sub-steps -- sponge(dt/2),
+ * relaxation(dt/2), the RK step as it is, relaxation(dt/2), sponge(dt/2), then the receiver record and the monitor sample
+ * (they see the synchronised state).  The sub-step solves u' = -sigma u, v' = -sigma v exactly: both fields, and with
+ * relaxation on the memory variables z_nu, are multiplied by g = exp(-sigma h), formed in double and rounded once to T.
+ * A scaling: unconditionally stable, it increases no quadratic energy, the stable_dt rules are untouched, and where
+ * sigma = 0 a DOF keeps its bits.  With constant sigma the linear models with relaxation commute with the scaling: a run
+ * with the sponge is exactly e^{-sigma t} times the run without it.
+ * Inside a layer v holds u_t + sigma u, not u_t; outside nothing changes.  The first-order condition on the outer face,
+ * acting on that v, is the matched condition of the damped medium: keep tag 2 on the faces behind the layers.  The
+ * nonlinear terms of the Westervelt model see that v too; amplitudes in a layer are small and nothing corrects for it.
+ * Two launches of one streaming kernel per step (profile name "sponge") over the tiles -- runs of 256 16-byte vectors of
+ * the internal vector -- that hold a nonzero sigma, (2 nrelax + 5) sizeof(T) bytes per DOF of those tiles, outside the
+ * graph of option "graph"; DOFs of other tiles are neither read nor written, and with the sponge off a step enqueues
+ * nothing new.
+ *   fus_model_set_sponge    sigma: T[ndofs] in caller numbering, host or device.  NULL or an all-zero sigma switches the
+ *                           sponge off and frees the plane and the tile list.  Legal once the setup is finished
+ *                           (FUS_ERR_STATE before) and between steps; u, v and the z_nu are kept.  A negative or
+ *                           non-finite value -> FUS_ERR_ARG, the model stays as it was.  Legal before or after
+ *                           fus_model_set_relaxation.
+ *   fus_model_sponge_get    sigma back, T[ndofs] in caller numbering.  FUS_ERR_STATE while the sponge is off.
+ *   fus_model_sponge_apply  one sub-step of length h >= 0 on the current state (what the stepping entries call).
+ *                           h < 0 or not finite -> FUS_ERR_ARG; sponge off, or neither fus_model_init nor fus_model_set
+ *                           before it -> FUS_ERR_STATE.
+ *   fus_model_sponge_info   DOFs with sigma > 0, listed tiles, tiles of the whole internal vector (any pointer may be NULL)
+ * Several ranks: nothing is summed over sharers, so the sub-step needs no exchange and no group finish call, and it
+ * works under RCCL, in an in-process group and under the external transport alike.  The contract: the sharers of a DOF
+ * pass the same sigma (a profile computed from coordinates does).  It is not checked across ranks. */
+int fus_model_set_sponge(fus_model* model, const void* sigma /* T[ndofs], 1/s, caller numbering; NULL: off */, int space);
+int fus_model_sponge_get(fus_model* model, void* out, int space);
+int fus_model_sponge_apply(fus_model* model, double h);
+int fus_model_sponge_info(fus_model* model, int64_t* ndofs_active, int64_t* ntiles_active, int64_t* ntiles_total);
+
 /* ---- bioheat: Pennes equation and CEM43 thermal dose on the operator's mesh ---------------------------------------
  * What a focused-ultrasound user computes from the pressure maps: the temperature rise the beam causes and the thermal
  * dose it leaves.  (The reference has no thermal model; this section replaces nothing there.)

@@ -330,6 +330,16 @@ public:
     check(fus_model_relaxation_get(h_, nu, z.data(), FUS_HOST));
     return z;
   }
+  // absorbing layers (fusmi.h): the damping rate sigma (1/s) per DOF in caller numbering, zero outside the layers; the
+  // sharers of a DOF on several ranks pass the same value.  u, v and the memory variables are kept.
+  void set_sponge(const std::vector<T>& sigma)
+  {
+    if (sigma.size() != (std::size_t)d_->ndofs())
+      throw Error(FUS_ERR_ARG, "set_sponge: one damping rate per DOF");
+    check(fus_model_set_sponge(h_, sigma.data(), FUS_HOST));
+  }
+  void clear_sponge() { check(fus_model_set_sponge(h_, nullptr, FUS_HOST)); }
+  void sponge_apply(double h) { check(fus_model_sponge_apply(h_, h)); }   // one sub-step on the current state
   fus_model* handle() const { return h_; }
   ~SpectralModel() { fus_model_destroy(h_); }
   SpectralModel(const SpectralModel&) = delete;
