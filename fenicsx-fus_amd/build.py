@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, "csrc", f) for f in ("fusmi.hip", "layout.cpp", "degree_unit.hip", "thermal.hip", "wave.hip")]
-DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("host.hpp", "core.hpp", "kernels.hpp", "wave_kernels.hpp", "thermal_kernels.hpp", "block_variant.hpp", "layout.hpp", "tables.hpp", "geom.hpp", "source_wave.hpp", "source_signal.hpp", "sts_coef.hpp", "thermal_bc.hpp", "thermal_owner.hpp", "thermal_response.hpp")] + [
+DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("host.hpp", "core.hpp", "kernels.hpp", "wave_kernels.hpp", "thermal_kernels.hpp", "block_variant.hpp", "layout.hpp", "tile_index.hpp", "tables.hpp", "geom.hpp", "source_wave.hpp", "source_signal.hpp", "sts_coef.hpp", "thermal_bc.hpp", "thermal_owner.hpp", "thermal_response.hpp")] + [
     os.path.join(HERE, "..", "include", "fusmi.h")]
 OUT = os.path.join(HERE, "fenicsxfus_amd", "libfusmi.so")
 

@@ -254,6 +254,31 @@ __device__ __forceinline__ float fast_rcp(float x)
   return r;
 }
 
+// 8-byte LDS reads of the element trips, issued singly.  hipcc's load/store optimiser merges neighbouring 8-byte reads
+// of one base register into ds_read2_b64, which costs the LDS array about 1.5 times what two ds_read_b64 cost (measured:
+// profiles/lds_trips.md, Part 0).  A volatile read through an LDS-address-space pointer is not merged: it becomes
+// ds_read_b64 with the constant offset folded, from the same base register, and the compiler still places the counted
+// waits.  (A generic volatile pointer would become flat_load.)  fp64 per-cell geometry kernels of the degrees <= 4,
+// where it was measured; fp32 reads stay as they are (ds_read2_b32 costs what two ds_read_b32 cost).
+// -DFUS_PROBE_LDS_PAIRED (developer probe) restores the merged form for an A/B.
+template <typename T, int N, int GEOM>
+__host__ __device__ constexpr bool lds_single_reads()
+{
+#ifdef FUS_PROBE_LDS_PAIRED
+  return false;
+#else
+  return sizeof(T) == 8 && GEOM != GEOM_STREAM && N <= 5;
+#endif
+}
+template <bool SINGLE, typename T>
+__device__ __forceinline__ T lds_rd(const T* __restrict__ p, int i)
+{
+  if constexpr (SINGLE && sizeof(T) == 8)
+    return ((const volatile T __attribute__((address_space(3)))*)p)[i];
+  else
+    return p[i];
+}
+
 // Lane-constant part of a trilinear cell's Jacobian for the lane's tensor column (X1, X2) = (pb, pc):
 // with x(X) = c0 + c100 X0 + c010 X1 + c001 X2 + c110 X0 X1 + c101 X0 X2 + c011 X1 X2 + c111 X0 X1 X2
 // the columns of J are  j0 = c100 + c110 X1 + c101 X2 + c111 X1 X2  (independent of X0),
@@ -263,13 +288,15 @@ template <typename T>
 struct TriLane
 {
   T j0[3], a1[3], d1[3], a2[3], d2[3];
+  template <bool SINGLE = false>   // SINGLE: cc is in LDS and its 8-byte reads are issued one by one (lds_rd)
   __device__ __forceinline__ void init(const T* __restrict__ cc, T pb, T pc)
   {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
     {
-      const T c100 = cc[i], c010 = cc[3 + i], c001 = cc[6 + i], c110 = cc[9 + i], c101 = cc[12 + i],
-              c011 = cc[15 + i], c111 = cc[18 + i];
+      const T c100 = lds_rd<SINGLE>(cc, i), c010 = lds_rd<SINGLE>(cc, 3 + i), c001 = lds_rd<SINGLE>(cc, 6 + i),
+              c110 = lds_rd<SINGLE>(cc, 9 + i), c101 = lds_rd<SINGLE>(cc, 12 + i), c011 = lds_rd<SINGLE>(cc, 15 + i),
+              c111 = lds_rd<SINGLE>(cc, 18 + i);
       d2[i] = c101 + pb * c111;
       j0[i] = (c100 + pb * c110) + pc * d2[i];
       a1[i] = c010 + pc * c011;
@@ -459,33 +486,23 @@ __device__ __forceinline__ void elem_compute2d(const ElemIn<T, N, OP, GEOM_STREA
   }
 }
 
-// Index of entry (i0, i1, i2) of an element's exchange tile in the re-mapped contractions.  N = 8: the tile is read and
-// written by lane (b, c) as (a, b, c) for every a, as (b, k, c) for every k and as (b, c, k) for every k; with a linear
-// image two of the three patterns put the 32 lanes of an LDS lane group on 4-8 banks (42 % of the LDS cycles of the
-// p=7 kernels were bank conflicts, profiles/r02_p7_remap_counters.json).  XOR-ing index 1 with the low bits of index
-// 0 and index 2 with index 1 makes all three conflict free, without padding.  Other N: planes of TS entries.
-// Plane stride of the exchange tile in the re-mapped contractions, and the entries reserved per element slot
-// (Layout::lds_bytes reserves the same).  N = 4: one entry of padding per plane; N = 8: XOR swizzle, no padding (rtix);
-// fp32 at N = 7 (the LDS-bound kernel of BASELINE configs[4]): planes of 56 -- 63 -> 56 bank-conflict cycles per element
-// over the three read patterns, by enumeration (ideal 42).
+// Exchange tile of the re-mapped contractions: plane stride, entries reserved per element slot (Layout::lds_bytes
+// reserves the same) and the index of entry (i0, i1, i2), all from tile_index.hpp, where the image is described.
 template <typename T, int N>
 __host__ __device__ constexpr int tile_plane_stride()
 {
-  return (N == 8 || N == 4) ? N * N + 1 : ((N == 7 && sizeof(T) == 4) ? 56 : N * N);
+  return fus::tile_plane_stride(N, (int)sizeof(T));
 }
 template <typename T, int N, int TD>
 __host__ __device__ constexpr int tile_slot_entries()
 {
-  return (TD == 3 && N == 7 && sizeof(T) == 4) ? N * 56 : (TD == 3 ? N * N * N : N * N) + N;
+  return fus::tile_slot_entries(N, (int)sizeof(T), TD);
 }
 
 template <int N, int TS>
 __device__ __forceinline__ int rtix(int i0, int i1, int i2)
 {
-  if constexpr (N == 8)
-    return i0 * 64 + ((i1 ^ (i0 & 3)) << 3) + (i2 ^ i1);
-  else
-    return i0 * TS + i1 * N + i2;
+  return fus::tile_index(N, TS, i0, i1, i2);
 }
 
 // Cross-lane reads without LDS (DPP modifiers of the vector ALU): lane l receives x of another lane of its 16-lane
@@ -604,6 +621,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
   // GEOM_TRILINEAR keeps the lane's rows / columns of the derivative table in LDS (read where used)
   // so that the kernel fits four waves per SIMD
   constexpr bool DLDS = (GEOM == GEOM_TRILINEAR) || (is_aff(GEOM) && (N == 6 || N == 7));
+  constexpr bool RD1 = lds_single_reads<T, N, GEOM>();   // the trips' 8-byte LDS reads one by one (lds_rd)
   if (in.er < 0)
     return;
   TriLane<T> tri;
@@ -618,7 +636,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
   }
 #else
   if (GEOM == GEOM_TRILINEAR)
-    tri.init(gc_l + in.er * 21, pb, pc);
+    tri.template init<RD1>(gc_l + in.er * 21, pb, pc);
 #endif
   int li[N];
 #pragma unroll
@@ -726,8 +744,8 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
     else if constexpr (GEOM == GEOM_DIAG)
     {
       constexpr int TS = tile_plane_stride<T, N>();
-      const T g0 = gc_l[in.er * 7 + 0] * cf * wbc, g1 = gc_l[in.er * 7 + 3] * cf * wbc,
-              g2 = gc_l[in.er * 7 + 5] * cf * wbc;   // w_b w_c of the lane's column, whichever two indices it spans
+      const T g0 = lds_rd<RD1>(gc_l, in.er * 7 + 0) * cf * wbc, g1 = lds_rd<RD1>(gc_l, in.er * 7 + 3) * cf * wbc,
+              g2 = lds_rd<RD1>(gc_l, in.er * 7 + 5) * cf * wbc;   // w_b w_c of the lane's column, whichever two indices it spans
 #pragma unroll
       for (int q = 0; q < N; ++q)
       {
@@ -746,8 +764,8 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
 #pragma unroll
       for (int k = 0; k < N; ++k)
       {
-        Tb[k] = sA[rtix<N, TS>(b, k, c)];
-        Uc[k] = sA[rtix<N, TS>(b, c, k)];
+        Tb[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, k, c));
+        Uc[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, c, k));
       }
       FUS_WAVE_SYNC();
 #pragma unroll
@@ -763,7 +781,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int a = 0; a < N; ++a)
-        Y[a] += sA[rtix<N, TS>(a, b, c)];
+        Y[a] += lds_rd<RD1>(sA, rtix<N, TS>(a, b, c));
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int q = 0; q < N; ++q)
@@ -778,7 +796,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int a = 0; a < N; ++a)
-        Y[a] += sA[rtix<N, TS>(a, b, c)];
+        Y[a] += lds_rd<RD1>(sA, rtix<N, TS>(a, b, c));
     }
 #ifdef FUS_ABL_NOEXCH   // developer ablation (wrong results): the six contractions and the transform on the lane's own
                          // registers, no exchange through the LDS tile and none of its wave barriers
@@ -859,9 +877,9 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       for (int k = 0; k < N; ++k)
       {
         if constexpr (!MF4)
-          Tb[k] = sA[rtix<N, TS>(b, k, c)];
+          Tb[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, k, c));
         if constexpr (!SWZ)
-          Uc[k] = sA[rtix<N, TS>(b, c, k)];
+          Uc[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, c, k));
       }
       if constexpr (MF4)
       {
@@ -885,7 +903,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int a = 0; a < N; ++a)
-        F1[a] = sA[rtix<N, TS>(a, b, c)];
+        F1[a] = lds_rd<RD1>(sA, rtix<N, TS>(a, b, c));
       }
       if constexpr (SWZ)
       {
@@ -909,9 +927,16 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int a = 0; a < N; ++a)
-        F2[a] = sA[rtix<N, TS>(a, b, c)];
+        F2[a] = lds_rd<RD1>(sA, rtix<N, TS>(a, b, c));
       }
-      // stiffness::transform (spectral_op.hpp:113-130)
+      // stiffness::transform (spectral_op.hpp:113-130); single reads: an affine cell's six numbers once per element
+      T Gc[6] = {};
+      if constexpr (RD1 && is_aff(GEOM))
+      {
+#pragma unroll
+        for (int gi = 0; gi < 6; ++gi)
+          Gc[gi] = lds_rd<RD1>(gc_l, in.er * 7 + gi);
+      }
 #pragma unroll
       for (int a = 0; a < N; ++a)
       {
@@ -932,7 +957,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
           for (int gi = 0; gi < 6; ++gi)
           {
             const int v = gi * N + a;
-            G6[gi] = (GEOM == GEOM_STREAM) ? in.g[v / VW][v % VW] : gc_l[in.er * 7 + gi] * w3[a];
+            G6[gi] = (GEOM == GEOM_STREAM) ? in.g[v / VW][v % VW] : (RD1 ? Gc[gi] : gc_l[in.er * 7 + gi]) * w3[a];
           }
           const T w0 = F0[a], w1 = F1[a], w2 = F2[a];
           F0[a] = cf * (G6[0] * w0 + G6[1] * w1 + G6[2] * w2);
@@ -963,7 +988,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int k = 0; k < N; ++k)
-        Tb[k] = sA[rtix<N, TS>(b, k, c)];
+        Tb[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, k, c));
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int j = 0; j < N; ++j)
@@ -979,7 +1004,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
 #pragma unroll
       for (int a = 0; a < N; ++a)
       {
-        T acc = sA[rtix<N, TS>(a, b, c)], dc[N];
+        T acc = lds_rd<RD1>(sA, rtix<N, TS>(a, b, c)), dc[N];
         dtab_row<T, N, 1>(Dk, a, dc);
 #pragma unroll
         for (int q = 0; q < N; ++q)
@@ -1002,7 +1027,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int k = 0; k < N; ++k)
-        Uc[k] = sA[rtix<N, TS>(b, c, k)];
+        Uc[k] = lds_rd<RD1>(sA, rtix<N, TS>(b, c, k));
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int j = 0; j < N; ++j)
@@ -1017,7 +1042,7 @@ __device__ __forceinline__ void elem_compute(const ElemIn<T, N, OP, GEOM>& in, c
       FUS_WAVE_SYNC();
 #pragma unroll
       for (int a = 0; a < N; ++a)
-        Y[a] += sA[rtix<N, TS>(a, b, c)];
+        Y[a] += lds_rd<RD1>(sA, rtix<N, TS>(a, b, c));
       }
     }
     else
