@@ -8,7 +8,8 @@
 //   block_variant(facts, traits, OP, STAGE) per launch: the template arguments (GEOM, TD, ATOMIC, MF, PK) of the kernel
 // op_build (fusmi.hip) calls op_traits with the geometry mode it predicts on the host, because the packed kernel's two
 // exchange-tile slots and the LDS budget shape the layout; op_setup_device calls it again with the mode the device
-// confirmed and with the layout's `pk` as given.  block_variant_exists() names the instantiations a library holds: the
+// confirmed and with the layout's `pk` as given, then op_traits_fit with the layout's largest block; block_walk() turns
+// that and the launch's grid into the kernel's WALK argument.  block_variant_exists() names the instantiations a library holds: the
 // launch dispatcher compiles exactly those, and block_variant() returns no other.
 #ifndef FUS_BLOCK_VARIANT_HPP
 #define FUS_BLOCK_VARIANT_HPP
@@ -88,7 +89,75 @@ struct OpTraits
   bool pk;    // packed fp32 variants in use (degrees 5-7: two elements per wave, layout slots doubled)
   bool diag;  // GEOM_AFFINE in its diagonal-metric form
   int gcs;    // per-cell geometry numbers the block keeps in LDS: 7 (affine), 21 (trilinear), 0 (streamed)
+  int fits = 0;   // bit nf - 1: every block of the layout fits the first batches of the kernels with nf operator
+                  // inputs (block_fits below; op_traits_fit sets it once the layout exists)
 };
+
+// ---- what one thread of the block kernel moves in its unrolled first batches (kernels.hpp, k_block_op) ----
+// first-batch prologue registers per thread at p = 7 (interior vectors) and at the degrees 8-10 (interior vectors, shared dofs)
+#ifndef FUS_UI_P7
+#define FUS_UI_P7 5
+#endif
+#ifndef FUS_UI_HI
+#define FUS_UI_HI 7
+#endif
+// The one definition of these capacities: the kernel sizes its batches by them, and the host decides by them
+// (block_fits) whether a layout may run the kernels that have no loop for what is left over.
+struct BlockCaps
+{
+  int ui;    // 16-byte interior vectors of the operator input
+  int us;    // shared dofs (gathered values in the prologue, partial sums in the epilogue)
+  int ul;    // 16-byte vectors of the local dofmaps
+  int gc;    // per-cell geometry numbers
+  bool gc_all;   // ... which are all of a block's (degree 4); false: the kernel keeps the loop for the rest -- the default
+                 // blocks of the degrees 2 and 3 (64 and 32 elements on 256 threads) hold more than two batches of them
+  int cf;    // cell coefficients
+  int epi;   // 16-byte interior ranges of the fused stage update in its two-range form (degrees <= 4, one operator
+             // input); 0: the kernel has another form, whose loop stays
+};
+constexpr BlockCaps block_caps(int P, int gcs, int nf)
+{
+  return {(P <= 3) ? 3 : ((P == 4) ? 2 : (P <= 6 ? 4 : (P == 7 ? FUS_UI_P7 : FUS_UI_HI))),
+          (P <= 3) ? 4 : ((P == 4) ? 3 : (P <= 7 ? 5 : FUS_UI_HI)),
+          (P <= 3) ? 2 : ((P == 4) ? 1 : 4),
+          gcs > 7 ? 2 : 1,
+          P == 4,
+          1,
+          (P <= 4 && nf == 1) ? 2 : 0};
+}
+
+// The kernels whose one-block form (WALK = 0) is compiled without leftover loops: fp64, per-cell geometry, degrees <= 4
+// (the kernels with range-checked accesses, k_block_op RANGED_FITS)
+constexpr bool straight_needs_fit(int P, int scalar_bytes, int geom)
+{
+  return geom != GEOM_STREAM && scalar_bytes == 8 && P <= 4;
+}
+
+// The largest block of a layout, and the threads of a workgroup
+struct BlockExtents
+{
+  int nthr;        // threads per workgroup (64 x waves)
+  int max_nint;    // interior dofs
+  int max_nsh;     // shared dofs (nloc - nint)
+  int max_nelem;   // elements
+  int nd;          // nodes per element
+};
+
+// Every block fits the first batches: nothing is left for a loop
+constexpr bool block_fits(int P, int gcs, int nf, const BlockExtents& e)
+{
+  const BlockCaps c = block_caps(P, gcs, nf);
+  const long long nthr = e.nthr, nvec = e.max_nint >> 1, n16 = ((long long)e.max_nelem * e.nd * 2 + 15) >> 4;
+  return nthr > 0 && nvec <= c.ui * nthr && e.max_nsh <= c.us * nthr && n16 <= c.ul * nthr
+         && (!c.gc_all || (long long)e.max_nelem * gcs <= c.gc * nthr) && e.max_nelem <= c.cf * nthr && (c.epi == 0 || nvec <= c.epi * nthr)
+         && (P + 1) * (P + 3) <= nthr;   // the derivative table with the 1-D weights and points: one entry per thread
+}
+
+// once the layout exists (op_setup_device)
+inline void op_traits_fit(OpTraits& t, int P, const BlockExtents& e)
+{
+  t.fits = (block_fits(P, t.gcs, 1, e) ? 1 : 0) | (block_fits(P, t.gcs, 2, e) ? 2 : 0);
+}
 
 // template arguments of k_block_op beside <T, P, OP, STAGE, NF>
 struct BlockVariant
@@ -157,6 +226,19 @@ inline BlockVariant block_variant(const OpFacts& f, const OpTraits& t, int op, i
       return {GEOM_DIAG, 3, atomic, 0, 0};
   }
   return {f.mode, 3, atomic, 0, 0};
+}
+
+// The template argument WALK of the variant's kernel for one launch with nf operator inputs.  1: the kernel with the
+// block loop and every leftover loop -- the only form of the streamed-geometry kernels, the form of a launch with
+// fewer workgroups than blocks (option "walk"), and the form of a layout with a block larger than the first batches of
+// a kernel whose one-block form has no leftover loops.  0: straight-line code for one block.
+inline int block_walk(const OpFacts& f, const OpTraits& t, const BlockVariant& v, int nf, bool fewer_groups_than_blocks)
+{
+  if (v.geom == GEOM_STREAM || v.td != 3 || fewer_groups_than_blocks)
+    return 1;
+  if (straight_needs_fit(f.P, f.scalar_bytes, v.geom) && !((t.fits >> (nf - 1)) & 1))
+    return 1;
+  return 0;
 }
 
 // The instantiations k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK> a library holds, for any NF

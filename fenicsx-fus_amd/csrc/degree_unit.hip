@@ -99,7 +99,9 @@ static int launch_block_op_v(fus_op* op, const T* geo, const T* coef, const T* x
     if (per_cu > 0)
       grid = std::min(blk_count, per_cu * op->ctx->num_cus);
   }
-  if (CAN_WALK && grid < blk_count)
+  // (block_variant.hpp: the kernel with the block loop also where a block of the layout is larger than the first
+  // batches of a straight-line kernel that has no leftover loops)
+  if (CAN_WALK && block_walk(op->facts, op->traits, BlockVariant{GEOM, TD, ATOMIC, MF, PK}, NF, grid < blk_count))
     hipLaunchKernelGGL((k_block_op<T, P, OP, ATOMIC, STAGE, NF, GEOM, TD, MF, PK, CAN_WALK ? 1 : W0>), dim3(grid),
                        dim3(64 * op->L.waves), op->lds_bytes, op->ctx->stream, K);
   else

@@ -340,6 +340,13 @@ static int op_setup_device(fus_op* op)
   else
     FUSCHK(ensure_stream_geometry<T>(op));
 
+  {
+    // does every block fit the first batches of the straight-line kernels (block_variant.hpp)?
+    BlockExtents e{64 * L.waves, 0, 0, L.max_nelem, L.Nd};
+    for (const Layout::Shape& s : L.shapes)
+      e.max_nint = std::max(e.max_nint, (int)s.nint), e.max_nsh = std::max(e.max_nsh, (int)(s.nloc - s.nint));
+    op_traits_fit(op->traits, op->P, e);
+  }
   FUSCHK(dalloc_bytes(pool, &op->d_partial, (size_t)(L.n_partial + L.n_shared) * sizeof(T), true, st));
   FUSCHK(dalloc_bytes(pool, &op->d_tmp_x, (size_t)L.n_internal * sizeof(T), true, st));
   FUSCHK(dalloc_bytes(pool, &op->d_tmp_b, (size_t)L.n_internal * sizeof(T), true, st));
@@ -1067,6 +1074,14 @@ int fus_op_uses_mfma4(fus_op* op)
   return uses_mf4(op->N, (int)op->ts, v.geom, v.mf) ? 1 : 0;
 }
 int fus_op_uses_pack32(fus_op* op) { return (op && op_variant(op).pk) ? 1 : 0; }
+int fus_op_uses_block_loop(fus_op* op)
+{
+  if (!op)
+    return 0;
+  // what a launch with one workgroup per block runs, with as many inputs as the operator was created for (option "walk"
+  // decides per launch, from the launch's number of blocks, whether it has fewer workgroups: not part of this answer)
+  return block_walk(op->facts, op->traits, op_variant(op), op->nfields == 2 ? 2 : 1, false);
+}
 
 int fus_op_info(fus_op* op, int64_t out[8])
 {

@@ -186,13 +186,7 @@ __host__ __device__ inline int64_t g_index(int v, int p)
 #define FUS_EPIU_F32P7AFF 2
 #endif
 // threads per workgroup the kernels of the degrees 5-10 are compiled for (256; 512 = developer probe of 8-wave blocks)
-// first-batch prologue registers per thread at p = 7 (interior vectors) and at the degrees 8-10 (interior vectors, shared dofs)
-#ifndef FUS_UI_P7
-#define FUS_UI_P7 5
-#endif
-#ifndef FUS_UI_HI
-#define FUS_UI_HI 7
-#endif
+// (first-batch prologue registers per thread, FUS_UI_P7 and FUS_UI_HI among them: block_variant.hpp, block_caps)
 #ifndef FUS_XCD_REMAP
 #define FUS_XCD_REMAP 0   // (measured: loses, see k_block_op)
 #endif
@@ -2603,7 +2597,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   // degree-4 fp64 ones went into scratch), and so did the fp32 trilinear kernels of degree 5 and one of degree 4,
   // compiled for four waves per SIMD.  Those keep the guarded form: a compare, an exec-mask branch and a zero-fill
   // per access.
-  constexpr bool RANGED_FITS = GEOM != GEOM_STREAM && sizeof(T) == 8 && P <= 4;
+  constexpr bool RANGED_FITS = straight_needs_fit(P, (int)sizeof(T), GEOM);
 #ifdef FUS_PROBE_GUARDED_LOADS   // developer probe (A/B of the range-checked prologue): the guarded form everywhere
   constexpr bool RANGED_PROLOGUE = false;
 #else
@@ -2619,9 +2613,16 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
   // registers are live across the epilogue of the previous block when a workgroup walks several blocks.
   // (p=7: 1098 interior vectors per 8-element block and 256 threads -> five; degrees 8-10: up to 1688 interior vectors and
   // 1538 shared dofs -> seven each: FUS_UI_HI.  With four, the remainder cost the prologue a second memory round trip.)
-  constexpr int UI = (P <= 3) ? 3 : ((P == 4) ? 2 : (P <= 6 ? 4 : (P == 7 ? FUS_UI_P7 : FUS_UI_HI))),
-                US = (P <= 3) ? 4 : ((P == 4) ? 3 : (P <= 7 ? 5 : FUS_UI_HI)),
-                UL = (P <= 3) ? 2 : ((P == 4) ? 1 : 4);
+  constexpr BlockCaps CAPS = block_caps(P, GCS, NF);   // (block_variant.hpp: the host decides by the same numbers)
+  constexpr int UI = CAPS.ui, US = CAPS.us, UL = CAPS.ul;
+  // WALK = 0 of the RANGED_FITS kernels runs only on layouts whose every block fits these batches (block_walk,
+  // block_variant.hpp): the loops for what a larger block leaves over are not compiled.  A layout with a larger block
+  // runs the WALK = 1 kernel, which has them all.
+#ifdef FUS_PROBE_LEFTOVER_LOOPS   // developer probe (A/B of the kernel without them): the loops everywhere
+  constexpr bool LEFTOVERS = true;
+#else
+  constexpr bool LEFTOVERS = WALK || !RANGED_FITS;
+#endif
   // ---- prologue: stage the block's dof values, local dofmaps and coefficients in LDS, clear the
   // accumulator.  Every load that does not depend on another is issued first (one round trip), the
   // gather of the shared dofs (it needs their indices) second (p_load); the LDS stores follow in p_commit.
@@ -2694,7 +2695,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       L.cf2v = (NF == 2) ? range_load<T>(range_rsrc(coef2 + M.elem_off, enable ? sh.nelem * TB : 0), tid * TB) : T(0);
       const __amdgpu_buffer_rsrc_t rgc = range_rsrc(geo + (int64_t)M.elem_off * GCS, (GCS && enable) ? ngc * TB : 0);
       L.gcv = GCS ? range_load<T>(rgc, tid * TB) : T(0);
-      L.gcv2 = (GCS > 7) ? range_load<T>(rgc, (tid + nthr) * TB) : T(0);
+      L.gcv2 = (CAPS.gc > 1) ? range_load<T>(rgc, (tid + nthr) * TB) : T(0);
       // derivative table, 1-D weights, 1-D points
       L.dgv = range_load<T>(range_rsrc(Dg, (with_tables && enable) ? (N2 + 2 * N) * TB : 0), tid * TB);
       // the shared dofs' values (their indices came with p_idx: 0 past the block's list, whose value p_commit leaves alone)
@@ -2724,7 +2725,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     L.cfv = (enable && tid < sh.nelem) ? coef[M.elem_off + tid] : T(0);
     L.cf2v = (NF == 2 && enable && tid < sh.nelem) ? coef2[M.elem_off + tid] : T(0);
     L.gcv = (enable && tid < ngc) ? geo[(int64_t)M.elem_off * GCS + tid] : T(0);
-    L.gcv2 = (GCS > 7 && enable && tid + nthr < ngc) ? geo[(int64_t)M.elem_off * GCS + tid + nthr] : T(0);
+    L.gcv2 = (CAPS.gc > 1 && enable && tid + nthr < ngc) ? geo[(int64_t)M.elem_off * GCS + tid + nthr] : T(0);
     L.dgv = (with_tables && enable && tid < N2 + 2 * N) ? Dg[tid] : T(0);  // derivative table, 1-D weights, 1-D points
     L.xtail = (enable && tid == 0 && (sh.nint & 1)) ? x[M.int_off + sh.nint - 1] : T(0);
     L.xtail2 = (NF == 2 && enable && tid == 0 && (sh.nint & 1)) ? x2[M.int_off + sh.nint - 1] : T(0);
@@ -2778,7 +2779,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     }
     if (tid < ngc)
       gc_l[tid] = L.gcv;
-    if (GCS > 7 && tid + nthr < ngc)
+    if (CAPS.gc > 1 && tid + nthr < ngc)
       gc_l[tid + nthr] = L.gcv2;
     if (with_tables)
     {
@@ -2789,16 +2790,17 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       if (GCS && tid >= N2 + N && tid < N2 + 2 * N)
         pt_l[tid - N2 - N] = L.dgv;
       // (a one-wave workgroup at the higher degrees has fewer threads than table entries)
-      for (int k = tid + nthr; k < N2 + 2 * N; k += nthr)
-      {
-        const T v = Dg[k];
-        if (k < N2)
-          D_l[k] = v;
-        else if (GCS && k < N2 + N)
-          w_l[k - N2] = v;
-        else if (GCS)
-          pt_l[k - N2 - N] = v;
-      }
+      if constexpr (LEFTOVERS)
+        for (int k = tid + nthr; k < N2 + 2 * N; k += nthr)
+        {
+          const T v = Dg[k];
+          if (k < N2)
+            D_l[k] = v;
+          else if (GCS && k < N2 + N)
+            w_l[k - N2] = v;
+          else if (GCS)
+            pt_l[k - N2 - N] = v;
+        }
     }
     if (tid == 0 && (sh.nint & 1))
     {
@@ -2816,69 +2818,73 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
       }
     // leftovers of large blocks (higher degrees), again with the loads of a batch ahead of its stores
     constexpr int UB = 8;
-    for (int base = tid + UI * nthr; base < nvec; base += nthr * UB)
+    if constexpr (LEFTOVERS)
     {
-      V2 v[UB], v2[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (base + u * nthr < nvec)
-        {
-          v[u] = xg[base + u * nthr];
-          if (NF == 2)
-            v2[u] = xg2[base + u * nthr];
-        }
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (base + u * nthr < nvec)
-        {
-          reinterpret_cast<V2*>(x_l)[base + u * nthr] = v[u];
-          if (NF == 2)
-            reinterpret_cast<V2*>(x2_l)[base + u * nthr] = v2[u];
-        }
-    }
-    for (int base = tid + US * nthr; base < nsh; base += nthr * UB)
-    {
-      int g[UB];
-      T v[UB], v2[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        g[u] = (base + u * nthr < nsh) ? gix[base + u * nthr] : 0;
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
+      for (int base = tid + UI * nthr; base < nvec; base += nthr * UB)
       {
-        v[u] = x[g[u]];
-        if (NF == 2)
-          v2[u] = x2[g[u]];
+        V2 v[UB], v2[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
+          if (base + u * nthr < nvec)
+          {
+            v[u] = xg[base + u * nthr];
+            if (NF == 2)
+              v2[u] = xg2[base + u * nthr];
+          }
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
+          if (base + u * nthr < nvec)
+          {
+            reinterpret_cast<V2*>(x_l)[base + u * nthr] = v[u];
+            if (NF == 2)
+              reinterpret_cast<V2*>(x2_l)[base + u * nthr] = v2[u];
+          }
       }
+      for (int base = tid + US * nthr; base < nsh; base += nthr * UB)
+      {
+        int g[UB];
+        T v[UB], v2[UB];
 #pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (base + u * nthr < nsh)
+        for (int u = 0; u < UB; ++u)
+          g[u] = (base + u * nthr < nsh) ? gix[base + u * nthr] : 0;
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
         {
-          x_l[sh.nint + base + u * nthr] = v[u];
+          v[u] = x[g[u]];
           if (NF == 2)
-            x2_l[sh.nint + base + u * nthr] = v2[u];
+            v2[u] = x2[g[u]];
         }
-    }
-    for (int base = tid + UL * nthr; base < n16; base += nthr * UB)
-    {
-      U4 q[UB];
 #pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (base + u * nthr < n16)
-          q[u] = lsrc[base + u * nthr];
+        for (int u = 0; u < UB; ++u)
+          if (base + u * nthr < nsh)
+          {
+            x_l[sh.nint + base + u * nthr] = v[u];
+            if (NF == 2)
+              x2_l[sh.nint + base + u * nthr] = v2[u];
+          }
+      }
+      for (int base = tid + UL * nthr; base < n16; base += nthr * UB)
+      {
+        U4 q[UB];
 #pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (base + u * nthr < n16)
-          reinterpret_cast<U4*>(ldm_l)[base + u * nthr] = q[u];
+        for (int u = 0; u < UB; ++u)
+          if (base + u * nthr < n16)
+            q[u] = lsrc[base + u * nthr];
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
+          if (base + u * nthr < n16)
+            reinterpret_cast<U4*>(ldm_l)[base + u * nthr] = q[u];
+      }
+      for (int k = tid + CAPS.cf * nthr; k < sh.nelem; k += nthr)
+      {
+        cf_l[k] = coef[M.elem_off + k];
+        if (NF == 2)
+          cf2_l[k] = coef2[M.elem_off + k];
+      }
     }
-    for (int k = tid + nthr; k < sh.nelem; k += nthr)
-    {
-      cf_l[k] = coef[M.elem_off + k];
-      if (NF == 2)
-        cf2_l[k] = coef2[M.elem_off + k];
-    }
-    for (int k = tid + (GCS > 7 ? 2 : 1) * nthr; k < ngc; k += nthr)
-      gc_l[k] = geo[(int64_t)M.elem_off * GCS + k];
+    if constexpr (LEFTOVERS || !CAPS.gc_all)
+      for (int k = tid + CAPS.gc * nthr; k < ngc; k += nthr)
+        gc_l[k] = geo[(int64_t)M.elem_off * GCS + k];
     // the round table (deterministic mode only) -> LDS, so the per-round element lookup is not a
     // global load that would drain the geometry prefetch queue (vmcnt retires in order)
     if (!ATOMIC)
@@ -3146,7 +3152,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     // degrees <= 4, one operator input: two interior ranges per pass, the loads of both in flight before
     // the first store (+1-3 % on the per-cell geometry paths; with the second input's extra operands
     // -- Westervelt -- it measured 5 % slower, and the higher degrees were not measured)
-    constexpr bool EPI2 = (P <= 4) && (NF == 1);
+    constexpr bool EPI2 = CAPS.epi != 0;
     struct Epi
     {
       bool on;
@@ -3272,7 +3278,7 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
     // at p=7 the one-range loop made the epilogue the longest phase of a block (6.9 of 19.2 us: a memory round trip per
     // pass).  Only where the kernel has registers to spare: at p=5 (compiled for four waves per SIMD) and on the streamed
     // kernels four ranges spill or cost a resident wave (-45 % / -30 %); profiles/r03_experiments.md section 11.
-    constexpr int EPIU = EPI2 ? 2 : epiu_of<T>(P, GEOM, NF);
+    constexpr int EPIU = EPI2 ? CAPS.epi : epiu_of<T>(P, GEOM, NF);
     constexpr bool EARLY = epi_early<T>(P);
     Epi Ef[EPIU];
     if (EARLY && STAGE != STAGE_NONE)
@@ -3352,23 +3358,25 @@ k_block_op(const KArgs<T, P + 1> kernel_args)
 #pragma unroll
     for (int u = 0; u < EPIU; ++u)
       epi_store(Ef[u]);
-    for (int i = tid + EPIU * nthr; i < nvec; i += EPIU * nthr)
-    {
-      Epi E[EPIU];
+    if constexpr (LEFTOVERS || !EPI2)
+      for (int i = tid + EPIU * nthr; i < nvec; i += EPIU * nthr)
+      {
+        Epi E[EPIU];
 #pragma unroll
-      for (int u = 0; u < EPIU; ++u)
-        epi_load(i + u * nthr, E[u], 0);
+        for (int u = 0; u < EPIU; ++u)
+          epi_load(i + u * nthr, E[u], 0);
 #pragma unroll
-      for (int u = 0; u < EPIU; ++u)
-        epi_store(E[u]);
-    }
+        for (int u = 0; u < EPIU; ++u)
+          epi_store(E[u]);
+      }
   }
 #pragma unroll
   for (int u = 0; u < US; ++u)
     if (ppv[u] >= 0)
       partial[ppv[u]] = (T)y_l[sh.nint + tid + u * nthr];
-  for (int k = tid + US * nthr; k < nsh; k += nthr)
-    partial[pp[k]] = (T)y_l[sh.nint + k];
+  if constexpr (LEFTOVERS)
+    for (int k = tid + US * nthr; k < nsh; k += nthr)
+      partial[pp[k]] = (T)y_l[sh.nint + k];
   }
   FUS_TRACE_END(blk);
   if (!WALK || !has_next)

@@ -99,7 +99,7 @@ class SpectralOperatorData:
         check(lib().fus_op_info(self.h, out))
         keys = ["nblocks", "interior_dofs", "shared_dofs", "pairs", "max_local_dofs", "shapes", "lds_bytes",
                 "internal_len"]
-        return dict(zip(keys, list(out)))
+        return dict(zip(keys, list(out)), block_loop=int(self.uses_block_loop()))
 
     def hmin(self) -> float:
         """Smallest local cell size (largest vertex distance per cell, dolfinx mesh::h; main.cpp:60-64)."""
@@ -135,6 +135,11 @@ class SpectralOperatorData:
 
     def uses_pack32(self) -> bool:
         return bool(lib().fus_op_uses_pack32(self.h))
+
+    def uses_block_loop(self) -> bool:
+        """The block kernel with the block loop and every leftover loop in launches with one workgroup per block: a block
+        too large for the straight-line kernel's first batches, or streamed geometry (include/fusmi.h)."""
+        return bool(lib().fus_op_uses_block_loop(self.h))
 
     def facet_diag(self, cells, local_facets, cellcoef):
         cells = np.ascontiguousarray(cells, dtype=np.int32)

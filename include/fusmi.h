@@ -194,6 +194,14 @@ int fus_op_uses_mfma4(fus_op* op);
 /* 1 when the fp32 stiffness kernel works on two elements per wave in packed float2 (degrees 5-7, per-cell
  * geometry paths, LDS-atomic accumulation; option "pack32"). */
 int fus_op_uses_pack32(fus_op* op);
+/* 1 when a launch of the operator with one workgroup per block runs the block kernel that keeps its block loop and
+ * every leftover loop: streamed geometry, or a layout with a block larger than the unrolled first batches of the
+ * straight-line kernel (fp64, per-cell geometry, degrees <= 4; lower block_elems to get that kernel back).  Answered
+ * for launches with as many inputs as the operator was created for (option "fields"): an operator created for two
+ * inputs also runs one-input launches (the mass action, the plain stiffness action), whose batches are larger and may
+ * fit where the two-input ones do not.  Option "walk" != 0 selects the same kernel per launch, wherever a launch has
+ * fewer workgroups than blocks; that choice depends on the launch's number of blocks and is not reported here. */
+int fus_op_uses_block_loop(fus_op* op);
 /* Smallest cell size of the local mesh, the size of a cell being its largest vertex-to-vertex
  * distance (dolfinx::mesh::h, linear_planewave2d_1/main.cpp:60-64); dt = CFL hmin / (c P^2), :102. */
 int fus_op_hmin(fus_op* op, double* hmin);
