@@ -470,6 +470,8 @@ static int op_build(fus_op* op, const uint8_t* force_shared)
   for (void* q : op->allocs)
     (void)hipFree(q);
   op->allocs.clear();
+  // (the gradient kernel's arrays were among them: gradient.hip allocates them again for the new layout)
+  op->d_grad_y = op->d_grad_part = op->d_grad_den = op->d_grad_coef = op->d_grad_in = nullptr, op->grad_in_bytes = 0;
   // centroids for the block partitioner
   std::vector<double> cen((size_t)op->ncells * 3, 0.0);
   const int nv = op->geom_nv;

@@ -157,6 +157,11 @@ struct fus_op
   // the pseudo partial slots (next-stage boundary terms of shared boundary dofs) live in d_partial,
   // i.e. per op, while several models may share one op: the model that wrote them last
   const struct fus_model* bnd_owner = nullptr;
+  // gradient / pair-product kernel (gradient.hip), allocated on its first use (all in allocs): the component sums in internal
+  // numbering T[tdim][n_internal], the partial planes of the shared dofs T[tdim][n_partial], the lumped M(1) 1,
+  // 16 rows of per-cell coefficients, and the inputs in internal numbering (d_grad_in only grows)
+  void *d_grad_y = nullptr, *d_grad_part = nullptr, *d_grad_den = nullptr, *d_grad_coef = nullptr, *d_grad_in = nullptr;
+  size_t grad_in_bytes = 0;
 };
 
 // -------------------------------------------------------------------------------------------------

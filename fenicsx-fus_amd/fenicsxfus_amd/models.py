@@ -51,6 +51,8 @@ class _SpectralExplicit:
         finally:
             self.ctx.set_option("forms", 0)
         check(lib().fus_model_set_rk_order(self.h, C.c_int(rk_order)))
+        self._c0, self._rho0 = c0a, rhoa          # radiation_force() forms alpha_k / (rho c w_k) from them
+        self._mon_nharm, self._mon_freq = 0, self.freq
         self.u_n = Function(self.V, dt_)
         self.v_n = Function(self.V, dt_)
         self._nrecv = 0
@@ -180,11 +182,13 @@ class _SpectralExplicit:
         w = _abi.FUS_U if which == "u" else _abi.FUS_V
         check(lib().fus_model_monitor(self.h, C.c_int(w), C.c_int(nharm), C.c_double(0.0 if freq is None else freq),
                                       C.c_int64(skip), C.c_int(every), C.c_int64(count)))
+        self._mon_nharm, self._mon_freq = (nharm, float(freq or self.freq)) if every else (0, self.freq)
 
     def monitor_off(self):
         """Stop sampling and free the accumulators."""
         check(lib().fus_model_monitor(self.h, C.c_int(_abi.FUS_U), C.c_int(0), C.c_double(0.0), C.c_int64(0), C.c_int(0),
                                       C.c_int64(0)))
+        self._mon_nharm = 0
 
     def monitor_info(self):
         """(number of samples, time of the first sample, time of the last sample)."""
@@ -201,6 +205,32 @@ class _SpectralExplicit:
         check(lib().fus_model_monitor_get(self.h, C.c_int(self._MON[name]), C.c_int(0 if k is None else k),
                                           ptr(f.x.array), C.c_int(_abi.FUS_HOST)))
         return f
+
+    # ---- intensity and radiation force from the monitor's harmonic maps, on the device (fusmi.h "intensity") ----
+    def _intensity(self, nharm, coef):
+        out = np.zeros((self.data.tdim, self.data.ndofs), dtype=self.data.dtype)
+        check(lib().fus_model_intensity(self.h, C.c_int(nharm), ptr(coef), ptr(out), C.c_int(_abi.FUS_HOST)))
+        return np.ascontiguousarray(out.T)
+
+    def intensity(self, nharm: int | None = None) -> np.ndarray:
+        """The time-averaged intensity vector ``I = sum_k (COS_k grad SIN_k - SIN_k grad COS_k) / (2 rho w_k)`` in W/m^2
+        over the harmonics 1..``nharm`` (default: all the monitor holds), recovered at the DOFs: an array (ndofs, tdim),
+        the shape output.write_vtu writes as a vector field.  The monitor must watch "u" and hold a sample; neither the
+        wave state nor the monitor changes."""
+        return self._intensity(self._mon_nharm if nharm is None else int(nharm), None)
+
+    def radiation_force(self, absorption) -> np.ndarray:
+        """The acoustic radiation force density ``F = sum_k 2 alpha_k I_k / c`` in N/m^3, (ndofs, tdim).  ``absorption``:
+        rows (K, ncells) in Np/m, one per harmonic (:func:`fenicsxfus_amd.monitor.power_law`), or 1-D for the fundamental
+        only."""
+        from .intensity import force_coef
+
+        a = np.atleast_2d(np.asarray(_array(absorption), dtype=np.float64))
+        if a.ndim != 2 or not 1 <= a.shape[0] <= 8 or a.shape[1] != self.data.ncells:
+            raise _abi.FusError(f"radiation_force: absorption must be (K, {self.data.ncells}) with K in 1..8 or one row, "
+                                f"got shape {a.shape}")
+        coef = force_coef(a, self._rho0.astype(np.float64), self._c0.astype(np.float64), self._mon_freq)
+        return self._intensity(a.shape[0], np.ascontiguousarray(coef, dtype=self.data.dtype))
 
     # ---- phased / apodised source: per-DOF amplitude and delay, optional tone burst (fusmi.h) ----
     def set_source(self, amplitude=None, delay=None, duration: float = 0.0):

@@ -81,6 +81,59 @@ class SpectralOperatorData:
     def mass(self, x, coeffs, y):
         return self._apply(lib().fus_mass_apply, x, coeffs, y)
 
+    # ---- gradient of a nodal field, recovered at the DOFs (fusmi.h "gradient") ----
+    def _grad_out(self, out):
+        if out is None:
+            return np.zeros((self.tdim, self.ndofs), dtype=self.dtype)
+        if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                and out.shape == (self.tdim, self.ndofs)):
+            raise ValueError(f"out must be a C-contiguous {np.dtype(self.dtype)} array of shape {(self.tdim, self.ndofs)}")
+        return out
+
+    def gradient_plan(self) -> dict:
+        """What a gradient call on this operator launches: kernel launches per call (1, or tdim component passes where a
+        block's accumulators do not fit LDS together), components per launch, threads per element group, LDS bytes."""
+        out = (C.c_int64 * 4)()
+        check(lib().fus_op_gradient_plan(self.h, out))
+        return dict(zip(("launches", "components", "group_threads", "lds_bytes"), list(out)))
+
+    def gradient(self, x, coeffs=None, nodal: bool = True, out=None):
+        """The gradient of the nodal field ``x`` as an array (tdim, ndofs).  ``nodal``: the recovered nodal gradient, the
+        lumped-mass L2 projection (``out`` is overwritten); else the weighted sums ``sum c_e |det J| w grad x`` are ADDED
+        to ``out`` (zeros when not given) with no sum over the ranks: the building block for a caller with its own
+        transport, who divides by the equally summed ``mass(1, 1)``.  ``coeffs``: one factor per cell (default 1)."""
+        x = np.ascontiguousarray(_array(x), dtype=self.dtype)
+        if x.shape != (self.ndofs,):
+            raise ValueError(f"gradient: expected {self.ndofs} values, one per DOF, got shape {x.shape}")
+        c = None
+        if coeffs is not None:
+            c = np.ascontiguousarray(_array(coeffs), dtype=self.dtype)
+            if c.shape != (self.ncells,):
+                raise ValueError(f"gradient: expected {self.ncells} coefficients, one per cell, got shape {c.shape}")
+        out = self._grad_out(out)
+        check(lib().fus_op_gradient(self.h, ptr(x), ptr(c), ptr(out),
+                                    C.c_int(_abi.FUS_GRAD_NODAL if nodal else _abi.FUS_GRAD_WEIGHTED), C.c_int(_abi.FUS_HOST)))
+        return out
+
+    def gradient_pairs(self, a, b, coeffs, nodal: bool = True, out=None):
+        """``sum_k coeffs[k] (a[k] grad b[k] - b[k] grad a[k])`` as an array (tdim, ndofs): ``a``, ``b`` (K, ndofs) with K in
+        1..8 (1-D: one pair), ``coeffs`` (K, ncells); ``nodal`` and ``out`` as in :meth:`gradient`."""
+        a = np.ascontiguousarray(np.atleast_2d(_array(a)), dtype=self.dtype)
+        b = np.ascontiguousarray(np.atleast_2d(_array(b)), dtype=self.dtype)
+        c = np.ascontiguousarray(np.atleast_2d(_array(coeffs)), dtype=self.dtype)
+        K = a.shape[0]
+        if a.ndim != 2 or not 1 <= K <= 8 or a.shape[1] != self.ndofs:
+            raise ValueError(f"gradient_pairs: a must be (K, {self.ndofs}) with K in 1..8, got shape {a.shape}")
+        if b.shape != a.shape:
+            raise ValueError(f"gradient_pairs: b must have a's shape {a.shape}, got {b.shape}")
+        if c.shape != (K, self.ncells):
+            raise ValueError(f"gradient_pairs: coeffs must be ({K}, {self.ncells}), one row per pair, got shape {c.shape}")
+        out = self._grad_out(out)
+        check(lib().fus_op_gradient_pairs(self.h, C.c_int(K), ptr(a), ptr(b), ptr(c), ptr(out),
+                                          C.c_int(_abi.FUS_GRAD_NODAL if nodal else _abi.FUS_GRAD_WEIGHTED),
+                                          C.c_int(_abi.FUS_HOST)))
+        return out
+
     def geometry(self):
         Nd = (self.P + 1) ** self.tdim
         G = np.empty((self.ncells, Nd, 6 if self.tdim == 3 else 3), dtype=self.dtype)

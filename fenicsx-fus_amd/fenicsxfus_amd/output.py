@@ -40,7 +40,8 @@ def subcell_connectivity(V) -> np.ndarray:
 
 
 def write_vtu(path: str, V, fields: dict, binary: bool = True) -> None:
-    """``fields``: name -> array [ndofs] (or object with ``.x.array``, like the models' ``u_n``)."""
+    """``fields``: name -> array [ndofs] (or object with ``.x.array``, like the models' ``u_n``), or [ndofs, tdim] for a
+    vector field."""
     x = np.asarray(V.tabulate_dof_coordinates(), dtype=np.float64)
     if x.shape[1] == 2:
         x = np.hstack([x, np.zeros((x.shape[0], 1))])
@@ -74,7 +75,12 @@ def write_vtu(path: str, V, fields: dict, binary: bool = True) -> None:
         f.write(array("types", types))
         f.write("</Cells>\n<PointData>\n")
         for k, v in data.items():
-            f.write(array(k, v))
+            if v.ndim == 2:   # a vector field [ndofs, tdim] (model.intensity()): three components, z = 0 on quadrilaterals
+                v3 = np.zeros((v.shape[0], 3), dtype=v.dtype)
+                v3[:, :v.shape[1]] = v
+                f.write(array(k, v3, 3))
+            else:
+                f.write(array(k, v))
         f.write("</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n")
 
 

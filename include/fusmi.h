@@ -331,6 +331,61 @@ int fus_model_monitor(fus_model* model, int which, int nharm, double freq, int64
 int fus_model_monitor_get(fus_model* model, int quantity, int k, void* out, int space);
 int fus_model_monitor_info(fus_model* model, int64_t* nsamples, double* t_first, double* t_last);
 
+/* ---- gradient: the sum-factorised gradient of a nodal field, recovered at the DOFs ---------------------------------
+ * Every other quantity the library reports is a function of a field at a point; these two calls differentiate one.
+ * Per element e the kernel gathers the field, takes the reference derivatives with the derivative table the stiffness
+ * action starts with (spectral_op.hpp:194-210), and at every GLL node q forms J(q), K = J^-1 and
+ *   (grad x)_e(q) = K(q)^T grad_xi x_e(q),        W_e(q) = |det J_e(q)| w_q   (the mass operator's factor),
+ * J from the cell's coordinates (trilinear / triquadratic, 2-D bilinear / biquadratic map), whatever geometry mode the
+ * operator runs in: no per-point geometry array is needed.  With (e,q)->i meaning that node q of element e is DOF i:
+ *   gradient:  y_d[i] += sum_{(e,q)->i} c_e W_e(q) (grad x)_{e,d}(q)
+ *   pairs:     y_d[i] += sum_{(e,q)->i} W_e(q) sum_{k<K} c_{k,e} [ a_k(i) (grad b_k)_{e,d}(q) - b_k(i) (grad a_k)_{e,d}(q) ]
+ * The recovered nodal value is the lumped-mass L2 projection g_d[i] = y_d[i] / sum_{(e,q)->i} W_e(q); the denominator is
+ * M(1) 1, computed once per operator with the mass action and kept.
+ * Arithmetic: the element work is done in T, the sums over the elements of a DOF in double for both scalar types and
+ * rounded to T once per block; the partial sums of a DOF that several blocks hold are added in T in ascending block order.
+ * The elements of a block are visited in the layout's conflict-free rounds, so the result is the same bits on every call,
+ * with or without the context option "deterministic".
+ * Every operator fus_op_create accepts is covered (degrees 2-10, both scalar types, both cell types and geometry orders,
+ * any block size); a block whose image does not fit LDS with all components runs one launch per component.
+ * fus_op_gradient_plan reports what a call on this operator launches: out[0] = kernel launches per call (1, or tdim
+ * component passes), out[1] = components per launch, out[2] = threads per element group, out[3] = LDS bytes per workgroup.
+ *   out     T[tdim][ndofs], component-major, caller numbering, `space`
+ *   mode    FUS_GRAD_WEIGHTED: out is ACCUMULATED with the weighted sums y_d -- no inter-rank reduction, the
+ *           fus_stiffness_apply convention: a caller with its own transport sums them over the sharers of a DOF and divides
+ *           by the equally summed fus_mass_apply(1, 1).
+ *           FUS_GRAD_NODAL: out is OVERWRITTEN with g_d (local denominators: complete on one rank)
+ *   coeffs  fus_op_gradient: T[ncells] or NULL (= 1); fus_op_gradient_pairs: T[npairs][ncells]
+ *   a, b    T[npairs][ndofs], caller numbering; npairs in 1..8
+ * FUS_ERR_ARG: a null pointer, npairs outside 1..8, a mode or space that does not exist. */
+enum { FUS_GRAD_WEIGHTED = 0, FUS_GRAD_NODAL = 1 };
+int fus_op_gradient(fus_op* op, const void* x, const void* coeffs, void* out, int mode, int space);
+int fus_op_gradient_pairs(fus_op* op, int npairs, const void* a, const void* b, const void* coeffs,
+                          void* out, int mode, int space);
+int fus_op_gradient_plan(fus_op* op, int64_t out[4]);
+
+/* ---- intensity: time-averaged intensity vector and radiation force from the monitor's harmonic maps -----------------
+ * For p_k(t) = C_k cos(w_k t) + S_k sin(w_k t) (C_k = FUS_MON_COS, S_k = FUS_MON_SIN, w_k = 2 pi k f) and the first-order
+ * momentum equation rho dw/dt = -grad p, the time-averaged intensity I = <p w> is
+ *   I = sum_k (C_k grad S_k - S_k grad C_k) / (2 rho w_k)          (p = A cos(w t - kappa x): A^2 / (2 rho c) along +x),
+ * the pair form above with a_k = C_k, b_k = S_k.  fus_model_intensity evaluates
+ *   out = nodal  sum_{k=1..nharm} coef[k-1][e] (C_k grad S_k - S_k grad C_k)
+ * on the device from the model's monitor accumulators: the kernel reads the double planes in place, scales them by 2 / n
+ * and rounds them to T exactly as fus_model_monitor_get does, then works in T -- the result is the pair form applied to
+ * the maps the caller could have pulled.
+ *   coef    NULL: 1 / (2 rho_e w_k) with the monitor's frequency f -- the intensity in W/m^2; else T[nharm][ncells] in
+ *           `space` (e.g. alpha_k / (rho c w_k): the radiation force density F = sum_k 2 alpha_k I_k / c in N/m^3)
+ *   out     T[tdim][ndofs], component-major, caller numbering, `space`
+ * The call alters neither the wave state nor any monitor accumulator: sampling may continue afterwards.
+ * FUS_ERR_ARG: a null model or out, nharm outside 1..8, a non-finite coef.  FUS_ERR_STATE: the monitor is off, watches
+ * FUS_V or has taken no sample yet (looked at before nharm's range, so a caller that asks for "all the monitor holds"
+ * with the monitor off gets this answer); it holds fewer harmonics than nharm; the model's operator has neighbours: the sums
+ * over the sharers of an interface DOF have no exchange here (fus_op_gradient_pairs with FUS_GRAD_WEIGHTED on pulled maps
+ * is the building block for a caller with its own transport).
+ * Lossy, Westervelt and relaxation models: rho dw/dt = -grad p is the first-order momentum equation; the viscous and
+ * nonlinear corrections to the particle velocity w are not modelled. */
+int fus_model_intensity(fus_model* model, int nharm, const void* coef, void* out, int space);
+
 /* ---- phased and apodised sources: per-DOF amplitude, delay and tone burst -----------------------------------------
  * The reference's source is one scalar g(t) times the diagonal facet weights of the tag-1 boundary (Linear.hpp:185-192,
  * :204-205), so every DOF of that boundary radiates with the same amplitude and phase.  This call gives each DOF d of it

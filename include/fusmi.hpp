@@ -157,6 +157,21 @@ public:
     check(fus_op_norm2(h_, x, loc, &v));
     return v;
   }
+  // gradient of the nodal field x, T[tdim][ndofs] component-major (fusmi.h "gradient"): nodal = the recovered nodal gradient;
+  // else the weighted sums, no sum over the ranks.  coeffs: T[ncells] or nullptr (= 1)
+  std::vector<T> gradient(const T* x, const T* coeffs = nullptr, bool nodal = true) const
+  {
+    std::vector<T> out((size_t)tdim_ * ndofs_, T(0));
+    check(fus_op_gradient(h_, x, coeffs, out.data(), nodal ? FUS_GRAD_NODAL : FUS_GRAD_WEIGHTED, FUS_HOST));
+    return out;
+  }
+  // sum_k coeffs[k] (a[k] grad b[k] - b[k] grad a[k]): a, b T[npairs][ndofs], coeffs T[npairs][ncells], npairs in 1..8
+  std::vector<T> gradient_pairs(int npairs, const T* a, const T* b, const T* coeffs, bool nodal = true) const
+  {
+    std::vector<T> out((size_t)tdim_ * ndofs_, T(0));
+    check(fus_op_gradient_pairs(h_, npairs, a, b, coeffs, out.data(), nodal ? FUS_GRAD_NODAL : FUS_GRAD_WEIGHTED, FUS_HOST));
+    return out;
+  }
 
 private:
   std::shared_ptr<Context> ctx_;
@@ -287,6 +302,17 @@ public:
     MonitorInfo i{0, 0.0, 0.0};
     check(fus_model_monitor_info(h_, &i.nsamples, &i.t_first, &i.t_last));
     return i;
+  }
+  // time-averaged intensity vector from the monitor's harmonic maps, on the device (fusmi.h "intensity"): T[tdim][ndofs],
+  // component-major.  coef empty: 1 / (2 rho w_k), W/m^2; else T[nharm][ncells], e.g. alpha_k / (rho c w_k) for the
+  // radiation force density in N/m^3
+  std::vector<T> intensity(int nharm, const std::vector<T>& coef = {}) const
+  {
+    if (!coef.empty() && coef.size() != (std::size_t)nharm * (std::size_t)d_->ncells())
+      throw Error(FUS_ERR_ARG, "intensity: coef must hold nharm rows of one value per cell");
+    std::vector<T> out((size_t)d_->tdim() * d_->ndofs());
+    check(fus_model_intensity(h_, nharm, coef.empty() ? nullptr : coef.data(), out.data(), FUS_HOST));
+    return out;
   }
   // phased / apodised source (fusmi.h): amplitude factor and delay per DOF (T[ndofs], caller numbering; nullptr = 1 / 0)
   // and the burst duration (0: continuous); all defaults restore the uniform source
