@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("fusmi.hip", "layout.cpp", "degree_unit.hip", "thermal.hip", "wave.hip", "gradient.hip")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("fusmi.hip", "layout.cpp", "degree_unit.hip", "thermal.hip", "wave.hip", "gradient.hip", "rayleigh.hip")]
 DEPS = SRC + [os.path.join(HERE, "csrc", f) for f in ("host.hpp", "core.hpp", "kernels.hpp", "wave_kernels.hpp", "thermal_kernels.hpp", "block_variant.hpp", "layout.hpp", "tile_index.hpp", "tables.hpp", "geom.hpp", "source_wave.hpp", "source_signal.hpp", "sts_coef.hpp", "thermal_bc.hpp", "thermal_owner.hpp", "thermal_response.hpp")] + [
     os.path.join(HERE, "..", "include", "fusmi.h")]
 OUT = os.path.join(HERE, "fenicsxfus_amd", "libfusmi.so")
@@ -22,7 +22,8 @@ DEGREES = (2, 3, 4, 5, 6, 7, 8, 9, 10)
 def _compile_units(objdir, degrees, extra, verbose):
     """degree_unit.hip is compiled once per polynomial degree and scalar type (-DFUS_TU_DEGREE=k -DFUS_TU_DTYPE=64|32:
     the block and geometry kernels of that degree), fusmi.hip (the operator), wave.hip (the wave models), thermal.hip (the
-    bioheat model) and gradient.hip (the gradient kernel: its degree is a run-time argument) once each, concurrently."""
+    bioheat model), gradient.hip (the gradient kernel: its degree is a run-time argument) and rayleigh.hip (the transducer
+    integral: no operator at all) once each, concurrently."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -32,7 +33,8 @@ def _compile_units(objdir, degrees, extra, verbose):
             ([hipcc, *FLAGS, *extra, "-c", SRC[1], "-o", os.path.join(objdir, "layout.o")]),
             ([hipcc, *FLAGS, *extra, "-c", SRC[3], "-o", os.path.join(objdir, "thermal.o")]),
             ([hipcc, *FLAGS, *extra, "-c", SRC[4], "-o", os.path.join(objdir, "wave.o")]),
-            ([hipcc, *FLAGS, *extra, "-c", SRC[5], "-o", os.path.join(objdir, "gradient.o")])]
+            ([hipcc, *FLAGS, *extra, "-c", SRC[5], "-o", os.path.join(objdir, "gradient.o")]),
+            ([hipcc, *FLAGS, *extra, "-c", SRC[6], "-o", os.path.join(objdir, "rayleigh.o")])]
     for k in degrees:
         for bits in (64, 32):
             jobs.append([hipcc, *FLAGS, *extra, f"-DFUS_TU_DEGREE={k}", f"-DFUS_TU_DTYPE={bits}", "-c", SRC[2], "-o",
@@ -48,7 +50,7 @@ def _compile_units(objdir, degrees, extra, verbose):
 
     workers = int(os.environ.get("FUSMI_BUILD_JOBS", min(len(jobs), os.cpu_count() or 1)))
     # heaviest units first so the pool stays busy
-    order = jobs[5:][::-1] + jobs[:5]
+    order = jobs[6:][::-1] + jobs[:6]
     with ThreadPoolExecutor(max_workers=workers) as ex:
         return list(ex.map(run, order))
 

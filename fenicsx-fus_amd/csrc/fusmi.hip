@@ -758,6 +758,12 @@ int fus_set_option(fus_ctx* c, const char* key, int64_t value)
       return fail(FUS_ERR_ARG, "walk must be -1 (auto), 0 (one workgroup per block) or 1..8 workgroups per CU");
     c->walk = (int)value;
   }
+  else if (!strcmp(key, "rayleigh_chunks"))
+  {
+    if (value < 0 || value > 1024)   // RAY_MAX_CHUNKS (rayleigh.hip)
+      return fail(FUS_ERR_ARG, "rayleigh_chunks must be 0 (auto) or 1..1024");
+    c->rayleigh_chunks = (int)value;
+  }
   else if (!strcmp(key, "mfma"))
   {
     if (value < -1 || value > 1)

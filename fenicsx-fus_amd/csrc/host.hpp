@@ -106,6 +106,7 @@ struct fus_ctx
   int diag_metric = 1;
   int walk = 0;   // block-kernel workgroups per CU that walk several blocks each (0: one workgroup per block --
                   // the measured best everywhere so far; -1: as many as are resident), see launch_block_op_v
+  int rayleigh_chunks = 0;   // source chunks of fus_rayleigh (rayleigh.hip): 0 = as many as fill the device, else forced
 };
 
 struct Neigh

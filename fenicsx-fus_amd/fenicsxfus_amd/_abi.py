@@ -16,6 +16,8 @@ FUS_LINEAR, FUS_LOSSY, FUS_WESTERVELT = 0, 1, 2
 FUS_U, FUS_V = 0, 1
 FUS_MON_MAX, FUS_MON_MIN, FUS_MON_MEAN, FUS_MON_RMS, FUS_MON_COS, FUS_MON_SIN = range(6)
 FUS_GRAD_WEIGHTED, FUS_GRAD_NODAL = 0, 1
+FUS_RAY_P, FUS_RAY_GRAD, FUS_RAY_RMIN = 1, 2, 4
+FUS_RAY_F64, FUS_RAY_MIXED = 0, 1
 FUS_TH_RISE, FUS_TH_DOSE, FUS_TH_HEAT, FUS_TH_DAMAGE, FUS_TH_PERFUSION = 0, 1, 2, 3, 4
 
 # every symbol include/fusmi.h declares
@@ -32,6 +34,7 @@ SYMBOLS = [
     "fus_model_set_receivers", "fus_model_sample", "fus_model_record", "fus_model_get_records",
     "fus_model_monitor", "fus_model_monitor_get", "fus_model_monitor_info",
     "fus_op_gradient", "fus_op_gradient_pairs", "fus_op_gradient_plan", "fus_model_intensity",
+    "fus_rayleigh", "fus_rayleigh_plan",
     "fus_model_set_source", "fus_model_set_source_weights", "fus_model_set_source_signals",
     "fus_model_set_relaxation", "fus_model_relaxation_get", "fus_model_relaxation_set", "fus_model_relaxation_apply", "fus_model_relaxation_strength",
     "fus_group_relaxation_finish",

@@ -52,6 +52,8 @@ class _SpectralExplicit:
             self.ctx.set_option("forms", 0)
         check(lib().fus_model_set_rk_order(self.h, C.c_int(rk_order)))
         self._c0, self._rho0 = c0a, rhoa          # radiation_force() forms alpha_k / (rho c w_k) from them
+        self._source_facets = (cells[tags == 1], lf[tags == 1])   # set_transducer() takes their DOFs
+        self._forms = forms
         self._mon_nharm, self._mon_freq = 0, self.freq
         self.u_n = Function(self.V, dt_)
         self.v_n = Function(self.V, dt_)
@@ -248,6 +250,50 @@ class _SpectralExplicit:
     def clear_source(self):
         """Back to the default source: the same g(t) at every DOF of the source boundary."""
         check(lib().fus_model_set_source(self.h, None, None, C.c_double(0.0), C.c_int(_abi.FUS_HOST)))
+
+    # ---- a transducer outside the mesh: the Rayleigh integral as the boundary drive (fusmi.h "transducers") ----
+    def source_scale(self) -> float:
+        """``scale`` of ``C = scale p0 w0 / s0``: 2 for Lossy / Westervelt with ``forms="cpp"`` (source doubled), else 1."""
+        return 2.0 if self._kind != _abi.FUS_LINEAR and self._forms == "cpp" else 1.0
+
+    def set_transducer(self, points, q, c: float, rho: float, alpha: float = 0.0, duration: float = 0.0, normal=None,
+                       precision: str = "f64"):
+        """Drive the source boundary (tag 1) with the field of a transducer outside the mesh: surface ``points [n, 3]``
+        with complex volume velocities ``q [n]`` (:mod:`fenicsxfus_amd.transducer`) in a coupling medium of sound speed
+        ``c``, density ``rho`` and absorption ``alpha`` (Np/m).  The Rayleigh integral with gradient and nearest
+        distance is evaluated on the device at the DOFs of the tag-1 facets and becomes the per-DOF amplitude and
+        delay of :meth:`set_source` (:func:`fenicsxfus_amd.transducer.drive`): the normal derivative where the source
+        facets carry no absorbing term (Linear; ``forms="python"``), the transparent combination where they do
+        (Lossy / Westervelt with ``forms="cpp"``), with ``C`` from the model's frequency, ``p0``, ``s0`` and source
+        scale; the delays are moved by whole periods to the arrival of the first wavelet.  ``normal``: the outward unit
+        normal(s) of the source boundary, [3] or one per source DOF in ascending DOF order; ``None`` fits a plane
+        through those DOFs (ValueError when they are not planar) and takes the side away from the mesh centroid.
+        Returns ``(P, amplitude, delay)`` on those DOFs (``self.transducer_dofs``); :meth:`clear_source` undoes it."""
+        from . import transducer as td
+
+        dofs = td.facet_dofs(self.V, *self._source_facets)
+        if len(dofs) == 0:
+            raise _abi.FusError("set_transducer: the model has no tag-1 (source) facets")
+        x = np.ascontiguousarray(np.asarray(self.V.tabulate_dof_coordinates(), dtype=np.float64)[dofs])
+        if normal is None:
+            nv = td.outward_normal(x, np.asarray(self.mesh.geometry.x, dtype=np.float64).mean(axis=0))
+        else:
+            nv = np.asarray(normal, dtype=np.float64)
+            if nv.shape not in ((3,), (len(dofs), 3)):
+                raise _abi.FusError(f"set_transducer: normal must be [3] or [{len(dofs)}, 3], got shape {nv.shape}")
+        P, gP, rmin = td.field(self.ctx, points, q, x, self.freq, c, rho, alpha, gradient=True, rmin=True,
+                               precision=precision)
+        scale = self.source_scale()
+        Cs = scale * self.p0 * 2.0 * np.pi * self.freq / self.s0
+        amp, tau = td.drive(P, gP, nv, self.freq, Cs, c=c, mode="transparent" if scale == 2.0 else "neumann",
+                            arrival=rmin / c)
+        if tau.min() < 0.0:   # whole periods: the phases stay
+            tau = tau + np.ceil(-tau.min() * self.freq) / self.freq
+        a, d = np.zeros(self.data.ndofs), np.zeros(self.data.ndofs)
+        a[dofs], d[dofs] = amp, tau
+        self.set_source(a, d, duration)
+        self.transducer_dofs = dofs
+        return P, amp, tau
 
     # ---- sources anywhere in the mesh, sampled drive signals (fusmi.h) ----
     def set_source_weights(self, w):

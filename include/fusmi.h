@@ -93,6 +93,8 @@ int fus_synchronize(fus_ctx* ctx);
  * planes at the dof's own index (no index list; every access coalesced) or through the shared-dof CSR; the
  * sums and their order are the same.  The CSR form is also taken when a dof has more sharing blocks than the
  * kernel has planes (16; a value k = 2..16 lowers that limit to k).
+ * "rayleigh_chunks" (0 (default) | 1..1024, any time): the number of source chunks fus_rayleigh splits its sum into; 0 = as
+ * many as fill the device (see "transducers").
  * Unknown keys -> FUS_ERR_ARG. */
 int fus_set_option(fus_ctx* ctx, const char* key, int64_t value);
 
@@ -416,6 +418,51 @@ int fus_model_intensity(fus_model* model, int nharm, const void* coef, void* out
  * Legal once the model's setup is finished (FUS_ERR_STATE before) and between steps; the state is kept.  Several ranks:
  * every sharer of a DOF passes the same values for it (they are functions of position). */
 int fus_model_set_source(fus_model* model, const void* amplitude, const void* delay, double duration, int space);
+
+/* ---- transducers: the Rayleigh integral of a radiating surface outside the mesh ------------------------------------
+ * A bowl or an array radiates into a homogeneous coupling medium (sound speed c, density rho, absorption alpha in Np/m;
+ * 0 for water) before its field reaches the meshed region.  With the time convention p(x,t) = Re[P(x) e^{-i w t}] --
+ * P = COS_1 + i SIN_1 in the monitor's terms -- and surface points x_s of complex volume velocity q_s = v_n(x_s) dA_s in
+ * m^3/s, w = 2 pi f, k = w / c, r_s = |x - x_s|:
+ *   P(x)      = -(i w rho / 2 pi) sum_s q_s e^{i k r_s} e^{-alpha r_s} / r_s
+ *   grad P(x) = -(i w rho / 2 pi) sum_s q_s (i k - alpha - 1/r_s) e^{i k r_s} e^{-alpha r_s} / r_s  (x - x_s) / r_s
+ * A pair with r_s == 0 contributes nothing; rmin then reports 0, so the caller can see it.  3-D only.
+ * fus_rayleigh evaluates this at ntgt targets.  It touches no operator or model; on several ranks each rank calls it
+ * for its own DOFs and nothing is exchanged.  Evaluated on the source face of a box and turned into per-DOF amplitude
+ * and delay (fenicsxfus_amd.transducer.drive) it is the boundary drive of fus_model_set_source: in steady state the
+ * tag-1 term is facet weight x g_d(t), g_d = a_d C cos(w (t - tau_d)) the outward normal derivative of p, so
+ * G = dP/dn_out where the source facets carry no absorbing term (FUS_LINEAR; Lossy / Westervelt with "forms" = 1) and
+ * G = dP/dn_out - (i w / c) P where they do ("forms" = 0), a_d = |G_d| / C, tau_d = arg(G_d) / w wrapped into [0, 1/f).
+ *
+ * Arithmetic, per (target, source) pair:
+ *   d = x - x_s, r2 = (dx dx + dy dy) + dz dz (every product and sum rounded: no fused multiply-add), r = sqrt(r2)   in double
+ *   t = r (f / c) revolutions, u = t - rint(t)         in double: the phase is reduced before any rounding to float
+ *   FUS_RAY_F64    s, c = sincospi(2 u); 1 / r; exp(-alpha r) (skipped when alpha == 0); e = exp(-alpha r) / r (c + i s);
+ *                  w = q e; with the gradient v = (i k - alpha - 1/r) w and v d_j / r -- all in double
+ *   FUS_RAY_MIXED  u, r, alpha r, q, d, k and alpha are rounded to float; sincospif, the reciprocal, the exponential
+ *                  and every product above are in float
+ * Both: the sums over s are kept in double, one target per thread, the sources taken in ascending order; the factor
+ * -i f rho (= -i w rho / 2 pi) multiplies the finished sums in double.  The output is always double.
+ * Chunks: where the targets are too few to fill the device (receivers, a small face) the sources are cut into
+ * `chunks` contiguous ranges of ceil(nsrc / chunks) points, one workgroup per (256 targets, chunk); the partial sums go
+ * to a workspace double[chunks][planes][ntgt] and a second kernel adds them in ascending chunk order (rmin: the
+ * smallest).  No atomics: two identical calls return the same bits.  Option "rayleigh_chunks" forces the count (clipped to
+ * nsrc); fus_rayleigh_plan reports out[0] = source chunks, out[1] = targets per workgroup, out[2] = kernel launches,
+ * out[3] = workspace bytes.
+ *   src_xyz  double[nsrc][3];  src_q double[nsrc][2] (re, im);  tgt_xyz double[ntgt][3]
+ *   what     FUS_RAY_P is always implied; out = double[planes][ntgt], plane-major: P_re, P_im; with FUS_RAY_GRAD
+ *            Px_re, Px_im, Py_re, Py_im, Pz_re, Pz_im; with FUS_RAY_RMIN the distance to the nearest source point
+ *   space    FUS_HOST | FUS_DEVICE, for all four arrays
+ * FUS_ERR_ARG, before anything is enqueued (out stays untouched): a null pointer; nsrc < 1 or ntgt < 1; a non-finite
+ * coordinate or q (checked where the arrays are on the host); freq, c or rho not positive; alpha negative; unknown
+ * bits in `what`, an unknown precision or space.  FUS_ERR_HIP names the bytes when the workspace or a staging buffer
+ * cannot be allocated. */
+enum { FUS_RAY_P = 1, FUS_RAY_GRAD = 2, FUS_RAY_RMIN = 4 };
+enum { FUS_RAY_F64 = 0, FUS_RAY_MIXED = 1 };
+int fus_rayleigh(fus_ctx* ctx, int64_t nsrc, const double* src_xyz, const double* src_q, int64_t ntgt,
+                 const double* tgt_xyz, double freq, double c, double rho, double alpha, int what, int precision,
+                 double* out, int space);
+int fus_rayleigh_plan(fus_ctx* ctx, int64_t nsrc, int64_t ntgt, int what, int64_t out[4]);
 
 /* ---- sources anywhere in the mesh: a source weight at any DOF -----------------------------------------------------
  * By default a DOF radiates only if it lies on a tag-1 boundary facet.  This call gives every DOF d a source weight

@@ -85,6 +85,33 @@ private:
   fus_ctx* h_ = nullptr;
 };
 
+// The Rayleigh integral of a radiating surface outside the mesh (fusmi.h "transducers"): src_xyz [nsrc][3], src_q [nsrc][2]
+// (re, im of the volume velocity), tgt_xyz [ntgt][3] on the host; returns double[planes][ntgt], plane-major: P_re, P_im; with
+// FUS_RAY_GRAD the six gradient planes; with FUS_RAY_RMIN the distance to the nearest source point.
+struct RayleighPlan
+{
+  std::int64_t chunks, targets_per_workgroup, launches, workspace_bytes;
+};
+inline RayleighPlan rayleigh_plan(const Context& ctx, std::int64_t nsrc, std::int64_t ntgt, int what = FUS_RAY_P)
+{
+  std::int64_t o[4];
+  check(fus_rayleigh_plan(ctx.handle(), nsrc, ntgt, what, o));
+  return {o[0], o[1], o[2], o[3]};
+}
+inline std::vector<double> rayleigh(const Context& ctx, const std::vector<double>& src_xyz, const std::vector<double>& src_q,
+                                    const std::vector<double>& tgt_xyz, double freq, double c, double rho, double alpha = 0.0,
+                                    int what = FUS_RAY_P, int precision = FUS_RAY_F64)
+{
+  const std::int64_t nsrc = (std::int64_t)(src_xyz.size() / 3), ntgt = (std::int64_t)(tgt_xyz.size() / 3);
+  if (src_xyz.size() != (std::size_t)nsrc * 3 || src_q.size() != (std::size_t)nsrc * 2 || tgt_xyz.size() != (std::size_t)ntgt * 3)
+    throw Error(FUS_ERR_ARG, "rayleigh: src_xyz [nsrc][3], src_q [nsrc][2] and tgt_xyz [ntgt][3] are expected");
+  const int planes = 2 + ((what & FUS_RAY_GRAD) ? 6 : 0) + ((what & FUS_RAY_RMIN) ? 1 : 0);
+  std::vector<double> out((std::size_t)planes * (std::size_t)ntgt);
+  check(fus_rayleigh(ctx.handle(), nsrc, src_xyz.data(), src_q.data(), ntgt, tgt_xyz.data(), freq, c, rho, alpha, what,
+                     precision, out.data(), FUS_HOST));
+  return out;
+}
+
 // What the reference's operator constructor derives from the function space (spectral_op.hpp:135-171):
 // tensor-ordered cell dofmap (reorder_dofmap, permute.hpp:15-42), 1-D GLL node coordinates in the
 // element's local order, mesh geometry.
